@@ -10,6 +10,12 @@ A step is one pass of the hot path over one synthetic, HBM-resident batch of BAS
 bucket when N > 1, Adam(amsgrad) step (train.py:117-121; the fused native FusedAdam by default,
 --optimizer torch for torch.optim.Adam).  Per-GPU work is fixed (weak scaling).
 Rank 0 prints ONE JSON line.  See DESIGN.md "Measurement".
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`).
+`--full` adds every other measurement after the timed steps: the instrumented per-kernel pass
+with its rooflines, the scatter-add, collation and inference legs and the CPU baseline (each
+still has its own switch).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy.
 """
 
 from __future__ import annotations
@@ -31,6 +37,7 @@ METRIC = "reactions/sec (fwd+bwd) depth=4 hidden=400 T1x batch; 1/2/4/8 MI355X"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_*_f32 dense peak
 BF16_MFMA_PEAK_TFLOPS = 2516.8  # 16 x the fp32 MFMA rate (MI355X_MICROARCH.md, dense)
+DUMP_BUDGET_BYTES = 48 * 2**20  # --dump-outputs writes at most this much array data
 
 
 def log(*a):
@@ -75,7 +82,21 @@ def parse():
                     help="diagnostic: time this many further blocks of --steps steps after the "
                          "timed one (per-step HIP events); not part of `value`")
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "traffic.json"))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement (instrumented "
+                         "per-kernel pass and rooflines, collation, inference, CPU baseline, "
+                         "--diag-blocks); without it only the headline figure is measured")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (predictions, loss, gradients, "
+                         "updated parameters) as DIR/<name>.npy; the timed steps then start from "
+                         "the initial weights, optimizer state and dropout counter, so the "
+                         "arrays do not depend on how long the warmup ran")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline figure only
+        args.collate_bench = args.infer_bench = args.cpu_baseline = 0
+        args.profile_steps = args.diag_blocks = 0
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -577,6 +598,35 @@ def cpu_baseline(cfgname, seconds, dropout):
                       f"{torch.get_num_threads()} threads"}
 
 
+def dump_outputs(out_dir, model, last):
+    """What a caller of the timed step holds after its last run, as <out_dir>/<name>.npy (fp32):
+    the predictions and the loss it returned, the gradients it left on the parameters and the
+    parameters Adam updated.  12 MB at cfg2, written whole; where the arrays exceed
+    DUMP_BUDGET_BYTES (sweep_max: 70 MB) every array above 64 Ki elements is written as the same
+    seeded sample of its flattened elements, scaled to fit."""
+    import numpy as np
+
+    arrays = {"pred": last["pred"], "loss": last["loss"]}
+    for k, p in model.named_parameters():
+        arrays["param." + k] = p
+        if p.grad is not None:
+            arrays["grad." + k] = p.grad
+    arrays = {k: t.detach().to("cpu", torch.float32).contiguous().numpy()
+              for k, t in arrays.items()}
+    big = {k for k, a in arrays.items() if a.size > 65536}
+    small_bytes = sum(4 * a.size for k, a in arrays.items() if k not in big)
+    big_bytes = sum(4 * arrays[k].size for k in big)
+    if small_bytes + big_bytes > DUMP_BUDGET_BYTES:
+        keep = (DUMP_BUDGET_BYTES - small_bytes) / big_bytes
+        for k in sorted(big):
+            a = arrays[k].reshape(-1)
+            idx = np.random.default_rng(0).choice(a.size, size=int(a.size * keep), replace=False)
+            arrays[k] = a[np.sort(idx)]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def _free_port() -> int:
     import socket
 
@@ -696,12 +746,23 @@ def main():
     else:
         loss_fn = torch.nn.MSELoss(reduction="sum")
 
+    last = {}  # the step's results (static tensors of the captured graph once it replays)
+
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = loss_fn(model(data), data.y)
+        pred = model(data)
+        loss = loss_fn(pred, data.y)
         loss.backward()
         opt.step()
+        if args.dump_outputs:
+            # detached: a kept loss would keep the step's autograd graph alive into the next step
+            last["pred"], last["loss"] = pred.detach(), loss.detach()
         return loss
+
+    initial = None
+    if args.dump_outputs:
+        initial = ([p.detach().clone() for p in model.parameters()],
+                   model._cgr_rng_counter.detach().clone())
 
     # warmup (eager), then optional graph capture of the whole step
     log(f"[bench] rank {rank}/{world} {args.config}: N={N} E={E} B={B} F={F_} H={H} D={D}")
@@ -775,6 +836,19 @@ def main():
         torch.cuda.synchronize()
         warm_extra += 3
 
+    if initial is not None:
+        # the warmup's length depends on the clock: put back, in place (the captured graph holds
+        # these addresses), the state the first step started from, so that the last timed step's
+        # results are the same from run to run
+        with torch.no_grad():
+            for p, p0 in zip(model.parameters(), initial[0]):
+                p.copy_(p0)
+            for st in opt.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+            model._cgr_rng_counter.copy_(initial[1])
+
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -793,6 +867,9 @@ def main():
         el = float(t.item())
     ms = el / args.steps * 1e3
     value = world * B * args.steps / el
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last)
 
     diag = None
     if args.diag_blocks > 0:
@@ -971,6 +1048,7 @@ def main():
         # (ddp.teardown explains the order)
         from cgr_mpnn_3D._amd.ddp import teardown
 
+        last.clear()  # tensors of the captured graph's pool
         run = g = None  # noqa: F841
         teardown(model, graphs_released=True)
 

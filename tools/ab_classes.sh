@@ -13,7 +13,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for v in ${VARIANTS}; do
     IFS=: read -r name lib envs <<< "$v"
     if [ -n "$lib" ]; then export CGR_MPNN3D_LIB=$lib; else unset CGR_MPNN3D_LIB; fi
-    timeout -k 10 300 env ${envs//,/ } python bench.py --config $CFG --steps 40 --warmup 10 --cpu-baseline 0 \
+    timeout -k 10 300 env ${envs//,/ } python bench.py --full --config $CFG --steps 40 --warmup 10 --cpu-baseline 0 \
       --collate-bench 0 --infer-bench 0 --profile-steps 10 > "$OUT/${name}_$r.json" \
       2> "$OUT/${name}_$r.err" || { tail -5 "$OUT/${name}_$r.err"; exit 1; }
     python - "$OUT/${name}_$r.json" "$name" "$r" <<'PY'

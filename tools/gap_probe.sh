@@ -12,7 +12,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for v in "drv:--steps 20 --warmup 5 --diag-blocks 10" "def:--steps 50 --warmup 30 --diag-blocks 4"; do
     name=${v%%:*}
     args=${v#*:}
-    timeout -k 10 300 python bench.py $args $EXTRA > "$OUT/${name}_$r.json" 2> "$OUT/${name}_$r.err" || exit $?
+    timeout -k 10 300 python bench.py --full $args $EXTRA > "$OUT/${name}_$r.json" 2> "$OUT/${name}_$r.err" || exit $?
     python - "$OUT/${name}_$r.json" "$name" "$r" <<'EOF'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -22,7 +22,7 @@ rc=$?; stage "pytest rc=$rc"; tail -25 "$OUT/pytest_gpu.log"
 
 if [ "${SKIP_BENCH:-0}" = "0" ]; then
   stage bench
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:---steps 30 --warmup 5 --cpu-seconds 8} \
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:---steps 30 --warmup 5 --cpu-seconds 8} \
     > "$OUT/bench.json" 2> "$OUT/bench.err"
   rc=$?; stage "bench rc=$rc"; cat "$OUT/bench.json"; tail -5 "$OUT/bench.err"
   [ $rc -eq 0 ] || exit $rc
@@ -33,7 +33,7 @@ if [ "${SKIP_PROF:-0}" = "0" ]; then
   # the bench command itself (graph-captured timed steps + the serial instrumented pass), so the
   # per-kernel averages here can be set against the bench line's roofline entry
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \
-    -- python bench.py --steps 20 --warmup 3 --cpu-baseline 0 ${PROF_ARGS:-} \
+    -- python bench.py --full --steps 20 --warmup 3 --cpu-baseline 0 ${PROF_ARGS:-} \
     > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err"
   rc=$?; stage "rocprof rc=$rc"
   find "$OUT/prof" -name "*stats*" | head

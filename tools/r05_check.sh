@@ -16,7 +16,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -v -p no:cacheprovider --time
   --timeout-method thread > "$OUT/pytest_gpu.txt" 2>&1; rc=$?
 tail -3 "$OUT/pytest_gpu.txt"; [ $rc -eq 0 ] || { grep -E "FAIL|Error|error" "$OUT/pytest_gpu.txt" | head -20; exit 1; }
 st "bench cfg2 (defaults)"
-timeout -k 10 400 python bench.py > "$OUT/bench_cfg2.json" 2> "$OUT/bench_cfg2.err" || { tail -5 "$OUT/bench_cfg2.err"; exit 1; }
+timeout -k 10 400 python bench.py --full > "$OUT/bench_cfg2.json" 2> "$OUT/bench_cfg2.err" || { tail -5 "$OUT/bench_cfg2.err"; exit 1; }
 python -c "import json; d=json.loads(open('$OUT/bench_cfg2.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'])"
 if [ "${UNPAIRED:-1}" = "1" ]; then
   st "unpaired timing"

@@ -20,7 +20,7 @@ if [ "${PART:-1}" = "1" ]; then
     --timeout-method thread > "$OUT/pytest_gpu.txt" 2>&1; rc=$?
   tail -2 "$OUT/pytest_gpu.txt"; [ $rc -eq 0 ] || exit 1
   st "bench cfg2 (defaults)"
-  timeout -k 10 400 python bench.py > "$OUT/bench_cfg2.json" 2> "$OUT/bench_cfg2.err" || exit 1
+  timeout -k 10 400 python bench.py --full > "$OUT/bench_cfg2.json" 2> "$OUT/bench_cfg2.err" || exit 1
   summ "$OUT/bench_cfg2.json"
   for r in 1 2 3; do
     st "driver command $r"
@@ -34,12 +34,12 @@ if [ "${PART:-1}" = "1" ]; then
 else
   for c in ${CONFIGS:-cfg4 cfg5 train_default sweep_b16 sweep_b64 sweep_d5 sweep_max}; do
     st "bench $c"
-    timeout -k 10 300 python bench.py --config $c --cpu-baseline 0 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || exit 1
+    timeout -k 10 300 python bench.py --full --config $c --cpu-baseline 0 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || exit 1
     summ "$OUT/bench_$c.json"
   done
   st "rocprofv3 kernel trace of the default bench command"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \
-    -- python bench.py --cpu-baseline 0 > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || exit 1
+    -- python bench.py --full --cpu-baseline 0 > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || exit 1
   st "PMC passes"
   TAG=$TAG bash tools/pmc_profile.sh || exit 1
   st "scatter-add PMC passes"

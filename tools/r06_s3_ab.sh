@@ -24,7 +24,7 @@ for r in $(seq 1 "${ROUNDS:-3}"); do
   done
 done
 if [ "${PROFILE:-1}" = "1" ]; then
-  PARGS="--config ${CFG:-cfg2} --steps 50 --warmup 30 --cpu-baseline 0 --collate-bench 0 --infer-bench 0 --profile-steps 10"
+  PARGS="--full --config ${CFG:-cfg2} --steps 50 --warmup 30 --cpu-baseline 0 --collate-bench 0 --infer-bench 0 --profile-steps 10"
   for v in base new; do
     if [ $v = base ]; then export CGR_MPNN3D_LIB=$PWD/$BASE_LIB; else unset CGR_MPNN3D_LIB; fi
     timeout -k 10 180 python bench.py $PARGS > "$OUT/${v}_prof.json" 2> "$OUT/${v}_prof.err" || exit 1

@@ -24,7 +24,7 @@ for r in $(seq 1 "${ROUNDS:-3}"); do
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], sys.argv[3], d['value'], d['ms_per_step'])" "$OUT/${name}_$r.json" "$name" "$r"
   done
 done
-PARGS="--config ${CFG:-cfg2} --steps 50 --warmup 30 --cpu-baseline 0 --collate-bench 0 --infer-bench 0 --profile-steps 10"
+PARGS="--full --config ${CFG:-cfg2} --steps 50 --warmup 30 --cpu-baseline 0 --collate-bench 0 --infer-bench 0 --profile-steps 10"
 for v in $VARIANTS; do
   name=${v%%:*}; lib=${v#*:}
   if [ -n "$lib" ]; then export CGR_MPNN3D_LIB=$PWD/$lib; else unset CGR_MPNN3D_LIB; fi

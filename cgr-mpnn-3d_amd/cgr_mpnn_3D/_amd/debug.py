@@ -53,6 +53,19 @@ class ArenaRun:
         t = self.arena[off:off + 4 * rows * cols].view(torch.float32).view(rows, cols)
         return t[:, :self.H] if cols == self.Hp else t
 
+    def ws_floats(self, name, rows, index=0):
+        """[rows, H] view of a backward-workspace buffer ("dpre" with the layer index, "dpre0",
+        "ds": cgr_gnn_workspace_offset) of the last backward(); ws_floats_padded keeps the Hp - H
+        pad columns."""
+        return self.ws_floats_padded(name, rows, index)[:, :self.H]
+
+    def ws_floats_padded(self, name, rows, index=0):
+        lib = native.load()
+        off = lib.cgr_gnn_workspace_offset(ctypes.byref(self.cfg), self.N, self.E, self.B,
+                                           name.encode(), index)
+        assert off >= 0, (name, index)
+        return self.ws[off:off + 4 * rows * self.Hp].view(torch.float32).view(rows, self.Hp)
+
     def backward(self, dy, params):
         lib = native.load()
         dev = dy.device

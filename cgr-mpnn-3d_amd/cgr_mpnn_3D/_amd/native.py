@@ -15,7 +15,7 @@ _LIB_NAME = "libcgr_mpnn3d.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CGR_MPNN3D_LIB", os.path.join(_HERE, "lib", _LIB_NAME))
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 TRAIN_DROPOUT, TRAIN_FOR_BACKWARD = 1, 2  # cgr_gnn_forward / _backward `training` bits
 MAX_DEPTH = 32
 ACT_RELU, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -73,6 +73,8 @@ SIGNATURES = [
     ("cgr_gnn_arena_bytes", c_int64, [POINTER(CgrGnnConfig), c_int64, c_int64, c_int64]),
     ("cgr_gnn_workspace_bytes", c_int64, [POINTER(CgrGnnConfig), c_int64, c_int64, c_int64]),
     ("cgr_gnn_arena_offset", c_int64,
+     [POINTER(CgrGnnConfig), c_int64, c_int64, c_int64, c_char_p, c_int32]),
+    ("cgr_gnn_workspace_offset", c_int64,
      [POINTER(CgrGnnConfig), c_int64, c_int64, c_int64, c_char_p, c_int32]),
     ("cgr_graph_prep", c_int32, [POINTER(CgrGnnConfig), POINTER(CgrBatch), c_void_p, c_void_p]),
     ("cgr_gnn_forward", c_int32,

@@ -428,6 +428,21 @@ int64_t cgr_gnn_arena_offset(const cgr_gnn_config* cfg, int64_t N, int64_t E, in
   return o == (size_t)-1 ? -1 : (int64_t)o;
 }
 
+int64_t cgr_gnn_workspace_offset(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B,
+                                 const char* name, int32_t index) {
+  if (validate_config(cfg) || name == nullptr) return -1;
+  const Dims d = make_dims(cfg, N, E, B);
+  const WorkspaceLayout W = workspace_layout(d);
+  const std::string n(name);
+  // only what gnn_backward_impl leaves complete in fp32 on every path (gnn_bwd.hip): dzn and Gs
+  // exist as e-images alone on the split-bf16 paths, dm holds hand-off rows only
+  if (n == "dpre" && index >= 0 && index < d.D)
+    return (int64_t)(W.dpre + (size_t)index * 4 * (size_t)d.E * (size_t)d.Hp);
+  if (n == "dpre0") return (int64_t)W.dh0;
+  if (n == "ds") return (int64_t)W.ds;
+  return -1;
+}
+
 int cgr_graph_prep(const cgr_gnn_config* cfg, const cgr_batch* b, void* arena, void* stream) {
   clear_stale_hip_error();
   int rc = validate_config(cfg);

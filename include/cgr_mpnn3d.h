@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CGR_ABI_VERSION 6
+#define CGR_ABI_VERSION 7
 #define CGR_MAX_DEPTH 32
 
 enum cgr_status {
@@ -124,6 +124,18 @@ int64_t cgr_gnn_workspace_bytes(const cgr_gnn_config* cfg, int64_t num_nodes, in
  * "h" / "a" / "pre".  Returns -1 for an unknown or absent buffer. */
 int64_t cgr_gnn_arena_offset(const cgr_gnn_config* cfg, int64_t num_nodes, int64_t num_edges,
                              int64_t num_graphs, const char* name, int32_t index);
+
+/* Byte offset of a named backward-workspace buffer (introspection for tests/debugging; ABI 7).
+ * Valid after cgr_gnn_backward has returned and its stream has been synchronised.  All buffers are
+ * fp32 in sorted edge order (rows of "dpre" / "dpre0") or node order ("ds"), leading dimension
+ * Hp = round_up(hidden, 4).  Names: "dpre" with `index` = conv layer l (0 .. depth-1): the
+ * gradient at layer l's pre-activation; "dpre0": the gradient at the edge init's pre-activation
+ * (written in place of the skip sum dh0); "ds": the gradient at the readout aggregate a_D,
+ * already divided by the in-degree under mean aggregation (what the top layer gathers at dst).
+ * Returns -1 for any other name: buffers that not every dispatch path materialises in fp32
+ * (dzn, Gs, dm) are not exposed. */
+int64_t cgr_gnn_workspace_offset(const cgr_gnn_config* cfg, int64_t num_nodes, int64_t num_edges,
+                                 int64_t num_graphs, const char* name, int32_t index);
 
 /* Index bookkeeping only (also run by cgr_gnn_forward): stable dst-sorted edge order, reverse
  * edge map, src/dst CSR, graph node ranges.  Replaces the implicit index handling of

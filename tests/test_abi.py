@@ -80,6 +80,21 @@ def test_arena_and_workspace_sizes_scale():
         assert off >= 0 and off < a1
         if name not in ("status",):
             assert off % 256 == 0
+    # the backward workspace's readable buffers: dpre of every layer, dpre0, ds
+    woffs = []
+    for name, idx in [("dpre", 0), ("dpre", 3), ("dpre0", 0), ("ds", 0)]:
+        off = lib.cgr_gnn_workspace_offset(ctypes.byref(c), 7680, 15360, 256, name.encode(), idx)
+        assert 0 <= off < w, (name, idx)
+        assert off % 256 == 0  # the layout aligns every buffer; layer strides are E * Hp * 4
+        woffs.append(off)
+    assert woffs[1] - woffs[0] == 3 * 15360 * 400 * 4 and len(set(woffs)) == 4
+    assert woffs[2] + 15360 * 400 * 4 <= w and woffs[3] + 7680 * 400 * 4 <= w
+    # unknown names, layers out of range, and buffers not every path materialises: -1
+    for name, idx in [("dpre", 4), ("dpre", -1), ("dzn", 0), ("Gs", 0), ("dm", 0), ("h", 0),
+                      ("", 0)]:
+        assert lib.cgr_gnn_workspace_offset(ctypes.byref(c), 7680, 15360, 256, name.encode(),
+                                            idx) == -1, (name, idx)
+    assert lib.cgr_gnn_workspace_offset(ctypes.byref(c), 7680, 15360, 256, None, 0) == -1
     assert lib.cgr_gnn_arena_offset(ctypes.byref(c), 7680, 15360, 256, b"pre", 1) == -1
     assert lib.cgr_gnn_arena_offset(ctypes.byref(c_silu), 7680, 15360, 256, b"pre", 1) > 0
 

@@ -280,15 +280,18 @@ def test_graph_prep_single_graph_batch_none(split, cuda_device, monkeypatch):
 RECONCILIATIONS = {}  # case -> ReLU decisions taken from the GPU (reported by _write_report)
 
 
-def _write_report():
+def _write_report(name="relu_reconciliations.json", payload=None):
+    """payload (default: RECONCILIATIONS) as JSON into the test report directory; shared with
+    tests/stagewise_common.py (stage_errors.json)."""
     import json
     import os
 
     d = os.environ.get("CGR_TEST_REPORT_DIR", "gpurun_out")
     try:
         os.makedirs(d, exist_ok=True)
-        with open(os.path.join(d, "relu_reconciliations.json"), "w") as f:
-            json.dump(RECONCILIATIONS, f, indent=1, sort_keys=True)
+        with open(os.path.join(d, name), "w") as f:
+            json.dump(RECONCILIATIONS if payload is None else payload, f, indent=1,
+                      sort_keys=True)
     except OSError:
         pass
 

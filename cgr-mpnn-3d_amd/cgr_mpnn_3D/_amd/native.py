@@ -15,7 +15,7 @@ _LIB_NAME = "libcgr_mpnn3d.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CGR_MPNN3D_LIB", os.path.join(_HERE, "lib", _LIB_NAME))
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 TRAIN_DROPOUT, TRAIN_FOR_BACKWARD = 1, 2  # cgr_gnn_forward / _backward `training` bits
 MAX_DEPTH = 32
 ACT_RELU, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -106,10 +106,17 @@ SIGNATURES = [
     ("cgr_adam_step", c_int32,
      [POINTER(CgrAdamTensor), c_int32, c_double, c_double, c_double, c_double, c_double, c_int32,
       c_int32, c_void_p]),
+    ("cgr_adam_step_lr_ptr", c_int32,
+     [POINTER(CgrAdamTensor), c_int32, c_void_p, c_double, c_double, c_double, c_double, c_int32,
+      c_int32, c_void_p]),
     ("cgr_collate", c_int32,
      [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
       c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p]),
+    ("cgr_collate_padded", c_int32,
+     [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+      c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("cgr_mse_loss_forward", c_int32,
      [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     ("cgr_mse_loss_backward", c_int32,
@@ -124,6 +131,7 @@ SIGNATURES = [
 ]
 
 DEVERR_UNPAIRED_SEEN, DEVERR_UNPAIRED_TIMEOUT = 4, 16  # cgr_device_errors bits
+PAD_OVERFLOW, PAD_ODD_EDGES, PAD_BAD_ID = 1, 2, 4  # cgr_collate_padded info[2] bits
 
 _lib = None
 _load_error: Exception | None = None

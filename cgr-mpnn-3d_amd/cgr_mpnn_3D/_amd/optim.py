@@ -7,8 +7,11 @@ keeps the same constructor, ``param_groups`` / ``state`` layout (``step``, ``exp
 ``exp_avg_sq``, ``max_exp_avg_sq``) and update rule, and performs the whole update in
 ``cgr_adam_step`` (csrc/optim.hip): one kernel over every tensor plus a tiny step-counter
 kernel.  Each tensor's ``state["step"]`` lives on the device (like ``capturable=True``), so a training step that
-includes ``optimizer.step()`` can be captured into a HIP graph and replayed; ``lr`` is read from
-``param_groups`` at each call (a graph replays the lr it was captured with, as torch's does).
+includes ``optimizer.step()`` can be captured into a HIP graph and replayed.  A float ``lr`` is
+read from ``param_groups`` at each call (a graph replays the lr it was captured with, as torch's
+does); an ``lr`` given as a 0-dim fp32 CUDA tensor, as ``torch.optim.Adam(lr=tensor,
+capturable=True)`` takes it, is read on the device by the kernel (``cgr_adam_step_lr_ptr``), so
+a scheduler that updates the tensor in place (``ExponentialLR``) is followed by every replay.
 Parameters must be fp32 CUDA tensors; there is no CPU fallback.
 """
 
@@ -25,7 +28,10 @@ from . import native
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  amsgrad=False, *, maximize=False):
-        if not 0.0 <= lr:
+        if isinstance(lr, torch.Tensor):
+            if lr.numel() != 1:
+                raise ValueError("Tensor lr must be 1-element")
+        elif not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= eps:
             raise ValueError(f"Invalid epsilon value: {eps}")
@@ -129,9 +135,19 @@ class FusedAdam(torch.optim.Optimizer):
             beta1, beta2 = group["betas"]
             tab = self._table(gi, ps, grads)
             dev = ps[0].device
+            lr = group["lr"]
+            if isinstance(lr, torch.Tensor):
+                # read on the device, never on the host: no sync, and a captured step follows a
+                # scheduler's in-place updates
+                if lr.device != dev or lr.dtype != torch.float32 or lr.numel() != 1:
+                    raise RuntimeError("FusedAdam: a tensor lr must be a 1-element float32 "
+                                       "tensor on the parameters' device")
+                entry, lr_arg = self._lib.cgr_adam_step_lr_ptr, lr.data_ptr()
+            else:
+                entry, lr_arg = self._lib.cgr_adam_step, float(lr)
             with native.device_guard(dev):
-                native.check(self._lib.cgr_adam_step(
-                    tab, len(ps), float(group["lr"]), float(beta1), float(beta2),
+                native.check(entry(
+                    tab, len(ps), lr_arg, float(beta1), float(beta2),
                     float(group["eps"]), float(group["weight_decay"]),
                     int(bool(group["amsgrad"])), int(bool(group["maximize"])),
                     native.stream_ptr(dev)))

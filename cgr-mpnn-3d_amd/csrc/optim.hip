@@ -30,6 +30,9 @@ struct AdamHyper {
   double lr, b1, b2;
   float w1, b2f, w2, eps, wd;  // (float)(1 - b1), (float)b2, (float)(1 - b2), ... as torch casts
   int amsgrad, maximize;
+  // lr as a device scalar (cgr_adam_step_lr_ptr: a scheduler updates it between replays of a
+  // captured step); null = the host value `lr` above
+  const float* lr_dev;
 };
 
 constexpr int kAdamThreads = 256;
@@ -83,7 +86,8 @@ __global__ __launch_bounds__(kAdamThreads) void k_adam(AdamGroup G, AdamHyper h)
     const double step = (double)G.step[t][0];
     const double bc1 = 1.0 - pow(h.b1, step);
     const double bc2 = 1.0 - pow(h.b2, step);
-    sc[0] = (float)(-(h.lr / bc1));
+    const double lr = h.lr_dev ? (double)h.lr_dev[0] : h.lr;
+    sc[0] = (float)(-(lr / bc1));
     sc[1] = (float)sqrt(bc2);
   }
   __syncthreads();
@@ -123,10 +127,9 @@ __global__ __launch_bounds__(kAdamThreads) void k_adam(AdamGroup G, AdamHyper h)
 
 using namespace cgr;
 
-extern "C" int cgr_adam_step(const cgr_adam_tensor* tensors, int32_t num_tensors, double lr,
-                             double beta1, double beta2, double eps, double weight_decay,
-                             int32_t amsgrad, int32_t maximize, void* stream) {
-  clear_stale_hip_error();
+static int adam_step(const cgr_adam_tensor* tensors, int32_t num_tensors, double lr,
+                     const float* lr_dev, double beta1, double beta2, double eps,
+                     double weight_decay, int32_t amsgrad, int32_t maximize, void* stream) {
   CGR_CHECK(num_tensors >= 0 && (num_tensors == 0 || tensors != nullptr),
             "cgr_adam_step: bad tensor table");
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -139,7 +142,8 @@ extern "C" int cgr_adam_step(const cgr_adam_tensor* tensors, int32_t num_tensors
                     (float)eps,
                     (float)weight_decay,
                     amsgrad ? 1 : 0,
-                    maximize ? 1 : 0};
+                    maximize ? 1 : 0,
+                    lr_dev};
   int dev = -1;
   SideStreams* ss = hipStreamGetDevice(st, &dev) == hipSuccess ? side_streams_of(dev) : nullptr;
   (void)hipGetLastError();
@@ -189,4 +193,22 @@ extern "C" int cgr_adam_step(const cgr_adam_tensor* tensors, int32_t num_tensors
     }
   }
   return flush();
+}
+
+extern "C" int cgr_adam_step(const cgr_adam_tensor* tensors, int32_t num_tensors, double lr,
+                             double beta1, double beta2, double eps, double weight_decay,
+                             int32_t amsgrad, int32_t maximize, void* stream) {
+  clear_stale_hip_error();
+  return adam_step(tensors, num_tensors, lr, nullptr, beta1, beta2, eps, weight_decay, amsgrad,
+                   maximize, stream);
+}
+
+extern "C" int cgr_adam_step_lr_ptr(const cgr_adam_tensor* tensors, int32_t num_tensors,
+                                    const float* lr, double beta1, double beta2, double eps,
+                                    double weight_decay, int32_t amsgrad, int32_t maximize,
+                                    void* stream) {
+  clear_stale_hip_error();
+  CGR_CHECK(lr != nullptr, "cgr_adam_step_lr_ptr: NULL lr");
+  return adam_step(tensors, num_tensors, 0.0, lr, beta1, beta2, eps, weight_decay, amsgrad,
+                   maximize, stream);
 }

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CGR_ABI_VERSION 7
+#define CGR_ABI_VERSION 8
 #define CGR_MAX_DEPTH 32
 
 enum cgr_status {
@@ -273,6 +273,14 @@ typedef struct cgr_adam_tensor {
 int cgr_adam_step(const cgr_adam_tensor* tensors, int32_t num_tensors, double lr, double beta1,
                   double beta2, double eps, double weight_decay, int32_t amsgrad,
                   int32_t maximize, void* stream);
+/* The same step with the learning rate read on the device (ABI 8): `lr` is a device fp32 scalar,
+ * as torch.optim.Adam(lr=tensor, capturable=True) keeps it.  A scheduler that updates the scalar
+ * in place (ExponentialLR of train.py:121) is then followed by a captured step's replays; the
+ * kernel widens the value to double where cgr_adam_step uses its double argument, so an lr that
+ * is exact in fp32 gives bit-identical updates on both entries. */
+int cgr_adam_step_lr_ptr(const cgr_adam_tensor* tensors, int32_t num_tensors, const float* lr,
+                         double beta1, double beta2, double eps, double weight_decay,
+                         int32_t amsgrad, int32_t maximize, void* stream);
 
 /* On-device collation (replaces torch_geometric.loader.DataLoader / Batch.from_data_list in
  * trainer.py:105-118 over the per-reaction Data of ChemDataset.py:81-94).  The store holds every
@@ -289,6 +297,37 @@ int cgr_collate(const int64_t* graph_ids, int64_t num_ids, const int64_t* node_p
                 int64_t num_edge_features, const float* y, float* x_out, int64_t* edge_index_out,
                 int64_t num_edges_out, float* edge_attr_out, int64_t* batch_out, int64_t* ptr_out,
                 float* y_out, void* stream);
+
+/* Fixed-shape collation (ABI 8): cgr_collate's batch followed by one pad graph, so every batch
+ * has the shapes node_cap / edge_cap (edge_cap even) whatever its graphs hold, and a captured
+ * training step can replay over ragged batches.  Every argument the batch depends on is device
+ * memory -- graph_ids [B], slot_weight [B] (the loss weight of each slot: 1 real, 0 filler) --
+ * and the grid depends on B and the capacities only.  With N_real / E_real the node / edge sums
+ * of the ids (reduced on the device):
+ *   rows [0, N_real) / [0, E_real) of x_out [node_cap, F], edge_index_out [2, edge_cap] (row
+ *     stride edge_cap), edge_attr_out [edge_cap, Fe], batch_out [node_cap] and ptr_out[0..B),
+ *     y_out[0..B): exactly cgr_collate's output; mask_out[0..B) = slot_weight;
+ *   the pad graph is slot B: P = node_cap - N_real nodes with x = 0, batch = B;
+ *     ptr_out[B] = N_real, ptr_out[B+1] = node_cap, y_out[B] = 0, mask_out[B] = 0 (ptr_out has
+ *     B + 2 entries, y_out / mask_out B + 1);
+ *   pad edge pair j < (edge_cap - E_real) / 2: edge E_real + 2j = (a -> b), edge E_real + 2j + 1 =
+ *     (b -> a) with a = N_real + j mod P, b = N_real + (j + 1) mod P, edge_attr = 0: reverse
+ *     pairs (rev(e) = e ^ 1) like the real edges;
+ *   info [4] int64 = N_real, E_real, status, 0.  Status bits: 1 = the batch does not fit
+ *     (N_real + 2 > node_cap or E_real > edge_cap), 2 = edge_cap - E_real is odd, 4 = an id
+ *     outside [0, num_graphs_all) (taken as an empty graph).  With bit 1 or 2 set the outputs
+ *     inside the capacities are unspecified; nothing is ever written outside them.
+ * The pad graph's loss weight is 0, so dy = 0 for slot B and it adds an exact 0 to every
+ * gradient as long as its forward values are finite: the caller bounds the pad in-degree
+ * (2 ceil(pairs / P)).  One launch. */
+int cgr_collate_padded(const int64_t* graph_ids, const float* slot_weight, int64_t num_ids,
+                       int64_t num_graphs_all, const int64_t* node_ptr, const int64_t* edge_ptr,
+                       const float* x, int64_t num_node_features, const int64_t* edge_index,
+                       int64_t num_edges_all, const float* edge_attr, int64_t num_edge_features,
+                       const float* y, int64_t node_cap, int64_t edge_cap, float* x_out,
+                       int64_t* edge_index_out, float* edge_attr_out, int64_t* batch_out,
+                       int64_t* ptr_out, float* y_out, float* mask_out, int64_t* info,
+                       void* stream);
 
 /* Training loss (replaces torch.nn.MSELoss(reduction="sum") of train.py:120 as trainer.py:142-143
  * applies it; reduction_mean != 0 is MSELoss(reduction="mean")).  input, target: device [n] fp32.

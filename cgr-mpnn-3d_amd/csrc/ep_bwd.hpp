@@ -95,17 +95,13 @@ struct EpLayerBwdSeg {
 
   // C: the tile's accumulators [BM][LDC] in LDS (column j of the tile = output column n0 + j);
   // sd[q]: dst of rows m0 - 1 + q (q < BM + 2; distinct negative sentinels outside [0, M)),
-  // followed by 16 words of scratch; RPP > 0: thread tid < RPP * C4 owns the float4 column group
-  // tid % C4 of rows tid / C4 + RPP * it; RPP == 0 (flat): pass it takes piece q = tid + NT * it
-  // of the tile's BM x C4, row q / C4, column group q % C4; pv[it] holds pre4 of pass it's piece;
-  // tile_id: this workgroup's tile (tm * tiles_n + tn)
-  template <int BM, int BN, int NT, int LDC, int EIT, int RPP>
+  // followed by 16 words of scratch; pass it takes piece q = tid + NT * it of the tile's BM x C4,
+  // row q / C4, column group q % C4; pv[it] holds pre4 of pass it's piece; tile_id: this
+  // workgroup's tile (tm * tiles_n + tn)
+  template <int BM, int BN, int NT, int LDC, int EIT>
   __device__ __forceinline__ void tile(const Pre (&pv)[EIT], float* C, const int* sd, int m0,
                                        int n0, int tile_id, int tid) const {
     constexpr int C4 = BN / 4;
-    constexpr bool FLAT = RPP == 0;
-    const bool eact = FLAT || tid < RPP * C4;
-    const int ec4 = FLAT ? 0 : (eact ? tid % C4 : 0), er0 = FLAT ? 0 : tid / C4;
     const int nrow = min(BM, M - m0);
     const bool paired = (*status & 4) == 0;
     int* scratch = const_cast<int*>(sd) + BM + 2;  // 16 words
@@ -128,17 +124,14 @@ struct EpLayerBwdSeg {
 #pragma unroll
       for (int it = 0; it < EIT; ++it) {
         int r, c4;
-        if constexpr (FLAT) {
+        {
           const int q = tid + NT * it;
           if (q >= BM * C4) break;
           r = q / C4;
           c4 = q - r * C4;
-        } else {
-          r = er0 + RPP * it;
-          c4 = ec4;
         }
         const int col = n0 + 4 * c4;
-        if (!eact || r >= nrow || col >= N) continue;
+        if (r >= nrow || col >= N) continue;
         const float4 x = *reinterpret_cast<const float4*>(&C[r * LDC + 4 * c4]);
         const int64_t i = m0 + r;
         if (!paired) {

@@ -13,29 +13,11 @@ struct EpStore {
   int64_t ld;
   int M, N;
   const float* bias;
-  // c % 4 == 0; columns >= N are dropped (ld >= round_up(N, 4) for internal buffers)
-  __device__ __forceinline__ void apply4(int r, int c, float4 v) const {
-    if (r >= M || c >= N) return;
-    if (bias) {
-      v.x += bias[c];
-      if (c + 1 < N) v.y += bias[c + 1];
-      if (c + 2 < N) v.z += bias[c + 2];
-      if (c + 3 < N) v.w += bias[c + 3];
-    }
-    float* o = C + (int64_t)r * ld + c;
-    if (c + 4 <= N && ((ld & 3) == 0)) {
-      *reinterpret_cast<float4*>(o) = v;
-    } else {
-      o[0] = v.x;
-      if (c + 1 < N) o[1] = v.y;
-      if (c + 2 < N) o[2] = v.z;
-      if (c + 3 < N) o[3] = v.w;
-    }
-  }
   // Epilogue protocol of the GEMM kernels: ctx(c) = the constants of the float4 column group at
   // c (loaded once per thread: the split-bf16 NT keeps one column group per thread), pre4(r, c) =
   // the row operands of one float4 piece (issued for a whole tile before the accumulators go
-  // through LDS), apply4p = the arithmetic and the stores.
+  // through LDS), apply4p = the arithmetic and the stores (c % 4 == 0; columns >= N are dropped,
+  // ld >= round_up(N, 4) for internal buffers).
   struct Ctx {
     float4 b;
   };
@@ -140,11 +122,7 @@ struct EpLayer {
   int layer;
   // internal [M, ld] buffers, ld % 4 == 0: whole float4 in bounds of the padded row; columns >= N
   // hold don't-care values (never read as data)
-  __device__ __forceinline__ void apply4(int r, int c, float4 v) const {
-    Ctx cx = ctx(c);
-    finish_ctx(cx);
-    apply4p<-1>(r, c, v, pre4(r, c), cx);
-  }
+  // ctx / pre4 / apply4p: the form the fp32 NT of gemm.hpp takes (tools/concurrency_probe.hip);
   // per column group: bias and the scalars (sigma, dropout key); per piece: h0, an unconditional
   // load from a clamped in-bounds address (no branch around the loads)
   struct Ctx {
@@ -170,10 +148,6 @@ struct EpLayer {
     const bool ok = r < M && c < N;
     return Pre{*reinterpret_cast<const float4*>(h0 + (ok ? (int64_t)r * ld + c : 0))};
   }
-  // A >= 0: the activation as a compile-time constant (the GEMM kernel switches on `act` once,
-  // outside its epilogue loop: kAct); A < 0: `act` at run time
-  static constexpr bool kAct = true;
-  template <int A = -1>
   __device__ __forceinline__ void apply4p(int r, int c, float4 v, const Pre& p,
                                           const Ctx& cx) const {
     if (r >= M || c >= N) return;
@@ -182,8 +156,11 @@ struct EpLayer {
     const float bv[4] = {cx.b.x, cx.b.y, cx.b.z, cx.b.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) z[k] = (z[k] + bv[k]) + cx.sg * h0v[k];
-    finish4<A>(r, c, make_float4(z[0], z[1], z[2], z[3]), cx);
+    finish4<-1>(r, c, make_float4(z[0], z[1], z[2], z[3]), cx);
   }
+  // A >= 0: the activation as a compile-time constant (the split-bf16 NT kernel switches on `act`
+  // once, outside its epilogue loop: kAct); A < 0: `act` at run time
+  static constexpr bool kAct = true;
   // pre = z -> act -> dropout -> h stored (and returned); the caller checked r < M, c < N
   template <int A = -1>
   __device__ __forceinline__ float4 finish4(int r, int c, float4 z4, const Ctx& cx) const {
@@ -238,18 +215,7 @@ struct EpLayerSeg : EpLayer {
   float* part;         // [tiles, 2, BN] their partial sums (slot_of)
   int* cnt;            // [nodes * tiles_n] tickets (zero on entry, left zero)
   int tiles_n;
-  // apply4p / apply4z that also return the stored h (rows / columns outside: v unchanged)
-  template <int A = -1>
-  __device__ __forceinline__ float4 apply4p_h(int r, int c, float4 v, const Pre& p,
-                                              const Ctx& cx) const {
-    if (r >= M || c >= N) return v;
-    float z[4] = {v.x, v.y, v.z, v.w};
-    const float h0v[4] = {p.h0.x, p.h0.y, p.h0.z, p.h0.w};
-    const float bv[4] = {cx.b.x, cx.b.y, cx.b.z, cx.b.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) z[k] = (z[k] + bv[k]) + cx.sg * h0v[k];
-    return this->template finish4<A>(r, c, make_float4(z[0], z[1], z[2], z[3]), cx);
-  }
+  // apply4z that also returns the stored h (rows / columns outside: z unchanged)
   template <int A = -1>
   __device__ __forceinline__ float4 apply4z_h(int r, int c, float4 z, const Ctx& cx) const {
     if (r >= M || c >= N) return z;
@@ -276,7 +242,12 @@ struct EpSplit2 {
   __host__ __device__ size_t side_lds_bytes() const {
     return (size_t)prep_one_lds_ints(prep.N, prep.E, prep.B) * 4;
   }
-  __device__ __forceinline__ void apply4(int r, int c, float4 v) const {
+  struct Ctx {};
+  __device__ __forceinline__ Ctx ctx(int) const { return Ctx{}; }
+  __device__ __forceinline__ void finish_ctx(Ctx&) const {}
+  struct Pre {};
+  __device__ __forceinline__ Pre pre4(int, int) const { return Pre{}; }
+  __device__ __forceinline__ void apply4p(int r, int c, float4 v, const Pre&, const Ctx&) const {
     if (r >= M || c >= 2 * H) return;
     if (c + 4 <= H) {
       *reinterpret_cast<float4*>(P + (int64_t)r * ld + c) = v;
@@ -292,14 +263,6 @@ struct EpSplit2 {
       }
     }
   }
-  struct Ctx {};
-  __device__ __forceinline__ Ctx ctx(int) const { return Ctx{}; }
-  __device__ __forceinline__ void finish_ctx(Ctx&) const {}
-  struct Pre {};
-  __device__ __forceinline__ Pre pre4(int, int) const { return Pre{}; }
-  __device__ __forceinline__ void apply4p(int r, int c, float4 v, const Pre&, const Ctx&) const {
-    apply4(r, c, v);
-  }
 };
 
 // readout with the x-part precomputed: hn = act((s W_n[:, F:]^T + Q) + b_n)   (GNN.py:106-107)
@@ -312,32 +275,14 @@ struct EpReadoutQ {
   int64_t ld;
   int M, N;
   int act;
-  struct Ctx {
-    float4 b;
-  };
-  __device__ __forceinline__ Ctx ctx(int c) const {
-    return Ctx{make_float4(bias[min(c, N - 1)], bias[min(c + 1, N - 1)], bias[min(c + 2, N - 1)],
-                           bias[min(c + 3, N - 1)])};
-  }
+  struct Ctx {};
   __device__ __forceinline__ void finish_ctx(Ctx&) const {}
-  struct Pre {
-    float4 q;
-  };
-  __device__ __forceinline__ Pre pre4(int r, int c) const {
-    const bool ok = r < M && c < N;
-    return Pre{*reinterpret_cast<const float4*>(Q + (ok ? (int64_t)r * ld + c : 0))};
-  }
+  struct Pre {};
   static constexpr bool kAct = true;  // see EpLayer
-  template <int A = -1>
-  __device__ __forceinline__ void apply4p(int r, int c, float4 v, const Pre& p,
-                                          const Ctx& cx) const {
-    if (r >= M || c >= N) return;
-    apply4z<A>(r, c, f4add(f4add(v, p.q), cx.b), cx);
-  }
   // the addend (Q + b) taken into the accumulators in MFMA layout (gemm_b3nt_kernel kAddend),
-  // z = (acc + Q) + b in apply4p's order
+  // z = (acc + Q) + b
   static constexpr bool kAddend = true;
-  __device__ __forceinline__ Ctx ctx_add() const { return Ctx{f4zero()}; }
+  __device__ __forceinline__ Ctx ctx_add() const { return Ctx{}; }
   __device__ __forceinline__ float add_row(int r, int c) const {
     return Q[(int64_t)(r < M ? r : M - 1) * ld + (c < N ? c : N - 1)];
   }
@@ -354,38 +299,6 @@ struct EpReadoutQ {
     if (zn) *reinterpret_cast<float4*>(zn + o) = make_float4(z[0], z[1], z[2], z[3]);
     *reinterpret_cast<float4*>(hn + o) =
         make_float4(act_fwd(z[0], ac), act_fwd(z[1], ac), act_fwd(z[2], ac), act_fwd(z[3], ac));
-  }
-  __device__ __forceinline__ void apply4(int r, int c, float4 v) const {
-    apply4p<-1>(r, c, v, pre4(r, c), ctx(c));
-  }
-};
-
-// edge_to_node readout (GNN.py:106-107): hn = act([x | s] W_n^T + b_n)
-struct EpReadout {
-  static constexpr bool kSeg = false;
-  const float* bias;
-  float* hn;
-  float* zn;  // nullptr for ReLU
-  int64_t ld;
-  int M, N;
-  int act;
-  __device__ __forceinline__ void apply4(int r, int c, float4 v) const {
-    if (r >= M || c >= N) return;
-    const int64_t o = (int64_t)r * ld + c;
-    float z[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) z[k] += bias[min(c + k, N - 1)];
-    if (zn) *reinterpret_cast<float4*>(zn + o) = make_float4(z[0], z[1], z[2], z[3]);
-    *reinterpret_cast<float4*>(hn + o) =
-        make_float4(act_fwd(z[0], act), act_fwd(z[1], act), act_fwd(z[2], act), act_fwd(z[3], act));
-  }
-  struct Ctx {};
-  __device__ __forceinline__ Ctx ctx(int) const { return Ctx{}; }
-  __device__ __forceinline__ void finish_ctx(Ctx&) const {}
-  struct Pre {};
-  __device__ __forceinline__ Pre pre4(int, int) const { return Pre{}; }
-  __device__ __forceinline__ void apply4p(int r, int c, float4 v, const Pre&, const Ctx&) const {
-    apply4(r, c, v);
   }
 };
 

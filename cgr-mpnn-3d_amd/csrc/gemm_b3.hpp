@@ -23,10 +23,18 @@
 //     The k permutation b3_kperm (lane group g holds k = 4g..4g+3 and 16+4g..16+4g+3) makes each
 //     fragment load two float4s whose four lane groups cover 64 contiguous bytes of the row.
 //   * workgroup = WAVES waves, wave w owns RF 16-row fragments and all NF 16-column fragments of
-//     the tile (BM = 16 WAVES RF rows x BN = 16 NF columns); B is double-buffered in LDS, A and B
-//     register-prefetched one k step ahead (unconditional in-bounds loads: no vmcnt(0) merges).
-//   * epilogue: accumulators -> LDS [BM][BN+4] -> float4 row pieces -> ep.apply4p, operand loads
-//     issued first (gemm_nt_kernel's pattern).
+//     the tile (BM = 16 WAVES RF rows x BN = 16 NF columns); B goes through three LDS buffers, A
+//     and B are loaded into registers two k steps ahead (unconditional in-bounds loads: no
+//     vmcnt(0) merges), and each step's loads, LDS stores and A split are spread over its MFMAs,
+//     which run over the column fragments in pairs.
+//   * the last k step has nothing left to stage: an addend epilogue (EpLayer, EpLayerSeg,
+//     EpReadoutQ) loads its addend (bias, skip term, Q) there, in MFMA layout, and adds it to the
+//     accumulators before they leave the registers.
+//   * epilogue: accumulators -> LDS [BM][BN+4] -> float4 row pieces.  The addend and whole-tile
+//     epilogues take the tile's pieces flat (piece tid + NT * pass, every lane busy); the layer
+//     forward applies and sums each dst segment of the tile in ONE pass over (segment, column
+//     group) items; the plain epilogues (EpSplit2, EpStoreRowScale) keep one column group per
+//     thread, whose constants and row operands are loaded before the accumulators go through LDS.
 #pragma once
 
 #include <type_traits>
@@ -102,15 +110,29 @@ __device__ __forceinline__ floatx4 b3_mfma(const b3_u4& a, const b3_u4& b, const
                                                  __builtin_bit_cast(b3_bf16x8, b), c, 0, 0, 0);
 }
 
-// acc += a.b over one 32-deep step from three-piece fragments, smallest terms first
-__device__ __forceinline__ floatx4 b3_mfma6(const b3_u4 (&a)[3], const b3_u4& b0, const b3_u4& b1,
-                                            const b3_u4& b2, floatx4 c) {
-  c = b3_mfma(a[1], b1, c);
-  c = b3_mfma(a[0], b2, c);
-  c = b3_mfma(a[2], b0, c);
-  c = b3_mfma(a[0], b1, c);
-  c = b3_mfma(a[1], b0, c);
-  return b3_mfma(a[0], b0, c);
+// One 32-deep step of a row fragment against a pair of column fragments, from three-piece
+// fragments: accx += a.b and (two) accy += a.c, six piece products each, smallest terms first,
+// the two chains alternating so that two independent accumulators are in flight.  A last, single
+// column (!two) passes its own accumulator as accy, which is then left alone.
+__device__ __forceinline__ void b3_mfma6x2(const b3_u4 (&a)[3], const b3_u4 (&b)[3],
+                                           const b3_u4 (&c)[3], bool two, floatx4& accx,
+                                           floatx4& accy) {
+  floatx4 x = accx;
+  floatx4 y = accy;
+  x = b3_mfma(a[1], b[1], x);
+  if (two) y = b3_mfma(a[1], c[1], y);
+  x = b3_mfma(a[0], b[2], x);
+  if (two) y = b3_mfma(a[0], c[2], y);
+  x = b3_mfma(a[2], b[0], x);
+  if (two) y = b3_mfma(a[2], c[0], y);
+  x = b3_mfma(a[0], b[1], x);
+  if (two) y = b3_mfma(a[0], c[1], y);
+  x = b3_mfma(a[1], b[0], x);
+  if (two) y = b3_mfma(a[1], c[0], y);
+  x = b3_mfma(a[0], b[0], x);
+  if (two) y = b3_mfma(a[0], c[0], y);
+  accx = x;
+  if (two) accy = y;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -207,11 +229,6 @@ template <class EP, class = void>
 struct b3_ep_addend : std::false_type {};
 template <class EP>
 struct b3_ep_addend<EP, std::void_t<decltype(EP::kAddend)>> : std::bool_constant<EP::kAddend> {};
-#ifdef CGR_NO_ADDEND
-template <class EP>
-struct b3_ep_addend_off : std::false_type {};
-#define b3_ep_addend b3_ep_addend_off
-#endif
 
 // epilogue functors with kAct = true apply an activation `act`: the kernel switches on it once,
 // outside its epilogue loop, and hands it to the functor as a template constant
@@ -252,38 +269,18 @@ struct B3NtShape {
   static_assert(LDS_BYTES == b3nt_lds_bytes(BM, BN), "b3nt_lds_bytes");
 };
 
-#ifndef CGR_B3_LDA
-#define CGR_B3_LDA 4
-#endif
-#ifndef CGR_B3_RA_FENCE
-#define CGR_B3_RA_FENCE 1
-#endif
-constexpr int B3_LDA = CGR_B3_LDA;  // B fragment groups read from LDS ahead of the MFMAs using them
-constexpr bool kB3ReadAheadFence = CGR_B3_RA_FENCE;
-#ifndef CGR_B3_STEP_ACC
-#define CGR_B3_STEP_ACC 0
-#endif
-constexpr bool kB3StepAcc = CGR_B3_STEP_ACC;
-#ifndef CGR_B3_FLAT
-#define CGR_B3_FLAT 1
-#endif
-constexpr bool kB3FlatEpilogue = CGR_B3_FLAT;  // flat epilogue passes + compact segment pass
-#ifndef CGR_B3_SEGMERGE
-#define CGR_B3_SEGMERGE 1
-#endif
-constexpr bool kB3SegMerge = CGR_B3_SEGMERGE;  // the forward's apply and segment sums in one pass
-
 // Pipeline (one barrier per k step, 3 LDS buffers for B):
 //   iteration ks computes step ks from LDS buffer ks % 3 and A fragments afr[ks & 1], and stages
 //   step ks+2's B block (registers -> buffer (ks+2) % 3, which step ks-1 read before the previous
-//   barrier) and step ks+1's A fragments (split into afr[(ks+1) & 1]); the global loads of A(ks+2)
-//   and B(ks+3) are issued at its start, so every load has a full step to land.
-//   Staggered halves (CGR_B3_STAGGER): waves 0 .. W/2-1 compute then stage, waves W/2 .. W-1
-//   stage then compute, so the two waves sharing a SIMD (w, w + W/2) keep the matrix pipe busy
-//   while the other one waits on its loads, writes LDS and splits.
-//   Column groups are processed in pairs (CGR_B3_JPAIR): the six-term chains of two groups
-//   alternate, two independent accumulators in flight.
+//   barrier) and step ks+1's A fragments (split into afr[(ks+1) & 1]); it also issues the global
+//   loads of A(ks+2) and B(ks+3), so every load has a full step to land.
+//   A step runs over the column fragments in pairs (b3_mfma6x2): each pair's B fragments come from
+//   a ring of registers read from LDS some fragments ahead, and each pair carries its share of
+//   the step's loads, LDS stores and the A split between its MFMAs (sched_group_barrier).
 //   Staging past the end writes a buffer nobody reads any more (unconditional, branch-free).
+//   The last step (the tail) has nothing to stage: its load slots take the epilogue's addend.
+//   Epilogue: see the passes below -- whole-tile functor, merged apply + segment pass (layer
+//   forward), flat apply pass (other addend epilogues), one column group per thread (plain).
 template <int WAVES, int RF, int NF, bool NOMASK, class AL, class EP>
 __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u4* __restrict__ Bimg,
                                                                int nimg, EP ep, int M, int N,
@@ -309,13 +306,17 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
   const int nk = (K + B3_BK - 1) / B3_BK;
   const int sw = fg ^ lds_swz(fr);  // lds_swz(16 j + fr) == lds_swz(fr)
 
-  // ---- epilogue mapping: one float4 column group per thread, rows er0 + RPP * it ----
+  // ---- epilogue mapping ----
   constexpr int C4 = BN / 4;
-  constexpr int RPP = NT / C4;                // rows per pass
-  constexpr int EIT = (BM + RPP - 1) / RPP;   // passes
   constexpr bool SEG = EP::kSeg;  // the epilogue also sums the tile's dst segments (EpLayerSeg)
   // the whole tile goes to the functor (EpLayerBwdSeg: ep_bwd.hpp)
   constexpr bool TILE = b3_ep_tile<EP>::value;
+  constexpr bool ADD = b3_ep_addend<EP>::value;
+  static_assert(ADD || !SEG, "the segment pass applies addend epilogues");
+  // Plain epilogues: one float4 column group per thread (its constants loaded once, in the
+  // prologue), rows er0 + RPP * it
+  constexpr int RPP = NT / C4;                // rows per pass
+  constexpr int EIT = (BM + RPP - 1) / RPP;   // passes
   static_assert(NT >= BM + 2 && RPP >= 1, "one dst per thread; one row group per pass");
   const bool eact = tid < RPP * C4;
   const int ec4 = eact ? tid % C4 : 0, er0 = tid / C4;
@@ -324,7 +325,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
   // are already in the accumulators; the whole-tile functors) take item q = tid + NT * it of the
   // tile's BM x C4 float4 pieces, row q / C4, column group q % C4 -- every lane busy in every
   // pass (at BM 128 x 52 groups: 13 passes of 512 instead of 15 passes of 468 lanes)
-  constexpr bool FLAT = kB3FlatEpilogue && (TILE || b3_ep_addend<EP>::value);
+  constexpr bool FLAT = TILE || ADD;
   constexpr int EITF = (BM * C4 + NT - 1) / NT;
   constexpr int EP_IT = FLAT ? EITF : EIT;
   // issued in the prologue behind the first operand loads, used after the main loop: the column
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
   int sdv = 0;
   bool sstart = true;  // row tid starts a dst segment in the tile (handoff.hpp seg_*)
   auto epilogue_consts = [&]() {
-    if constexpr (b3_ep_addend<EP>::value)
+    if constexpr (ADD)
       cx = ep.ctx_add();  // the column constants travel with the addend
     else
       cx = ep.ctx(ecol);
@@ -408,141 +409,11 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
 #pragma unroll
     for (int j = 0; j < NF; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
 
-  // read-ahead depth: 2 groups at 11 fragment columns (4 spill the gathered-A kernels there)
-  constexpr int LDA = NF == 11 ? 2 : (B3_LDA < NF ? B3_LDA : NF - 1);
-  // One step: the MFMAs of step ks (LDS buffer cb, fragments afc), column groups in pairs, with
-  // the step's other work spread over them (the vector-memory path and the matrix pipe overlap
-  // only when loads are interleaved with the MFMAs; issued as one burst per step they stall every
-  // wave of the workgroup at once): the global loads of the next raw set (A(ksa) -> ya,
-  // B(ksb) -> yb), the LDS stores of the current set's B block (xb -> buffer wb) and the split of
-  // its A fragments (xa -> afn, step ksn).
-  constexpr int AV = (int)(sizeof(typename AL::Raw) / 16);  // VMEM instructions per A fetch unit
-  constexpr int NAS = RF * 2;                               // A fetch units per step
-  constexpr int NLS = NAS + BPT;                            // load slots per step
-  constexpr int NP = (NF + 1) / 2;                          // MFMA pairs per step
-  auto step = [&](int cb, const b3_u4 (&afc)[RF][3], const BRaw& xb, int wb, const ARaw& xa,
-                  b3_u4 (&afn)[RF][3], int ksn, ARaw& ya, int ksa, BRaw& yb, int ksb) {
-    const b3_u4* Bs = b3_lds + cb * BU4;
-    const int kba = ksa * B3_BK + 4 * fg;
-    const b3_u4* bsrc = Bimg + (size_t)(ksb < nk ? ksb : nk - 1) * 3 * nimg * 4;
-    auto load_slot = [&](int s) {
-      if (s < NAS) {
-        ya[s >> 1][s & 1] = al.fetch(arow[s >> 1], kba + 16 * (s & 1), K);
-      } else {
-        yb[s - NAS] = bsrc[boff[s - NAS]];
-      }
-    };
-    constexpr int RING = LDA + 2;
-    b3_u4 bq[RING][3];
-    auto rd = [&](int j) {
-      const int o = (j * 16 + fr) * 4 + sw;
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        bq[j % RING][q] = Bs[q * BN * 4 + o];
-    };
-#pragma unroll
-    for (int j = 0; j < LDA; ++j) rd(j);
-    // the read-ahead is issued here, ahead of everything (else the scheduler fills each pair's
-    // ds_read group with that pair's own reads and waits on them right away)
-    if constexpr (kB3ReadAheadFence) __builtin_amdgcn_sched_barrier(0);
-    floatx4 carx[RF], cary[RF];  // kB3StepAcc: the previous pair's step sums
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int j = 2 * p;
-      const bool two = j + 1 < NF;
-      int nrd = 0;
-      if (j + LDA < NF) {
-        rd(j + LDA);
-        nrd += 3;
-      }
-      if (two && j + 1 + LDA < NF) {
-        rd(j + 1 + LDA);
-        nrd += 3;
-      }
-      const b3_u4(&b)[3] = bq[j % RING];
-      const b3_u4(&c)[3] = bq[(j + 1) % RING];
-#pragma unroll
-      for (int i = 0; i < RF; ++i) {
-        // kB3StepAcc: the step's six products into a zero accumulator, then one fp32 add into
-        // the running sum (the matrix core aligns every product of an MFMA to its largest
-        // operand, accumulator included: the small pieces' products would be rounded at the
-        // running sum's ulp, tools/diag/bf16_round_probe.hip).  The add of pair p is issued
-        // behind pair p + 1's MFMAs (carry): only two pairs' temporaries are live.
-        floatx4 x = kB3StepAcc ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[i][j];
-        floatx4 y = kB3StepAcc ? x : (two ? acc[i][j + 1] : x);
-        x = b3_mfma(afc[i][1], b[1], x);
-        if (two) y = b3_mfma(afc[i][1], c[1], y);
-        x = b3_mfma(afc[i][0], b[2], x);
-        if (two) y = b3_mfma(afc[i][0], c[2], y);
-        x = b3_mfma(afc[i][2], b[0], x);
-        if (two) y = b3_mfma(afc[i][2], c[0], y);
-        x = b3_mfma(afc[i][0], b[1], x);
-        if (two) y = b3_mfma(afc[i][0], c[1], y);
-        x = b3_mfma(afc[i][1], b[0], x);
-        if (two) y = b3_mfma(afc[i][1], c[0], y);
-        x = b3_mfma(afc[i][0], b[0], x);
-        if (two) y = b3_mfma(afc[i][0], c[0], y);
-        if constexpr (kB3StepAcc) {
-          if (p > 0) {
-            acc[i][j - 2] += carx[i];
-            acc[i][j - 1] += cary[i];  // the previous pair always has two columns
-          }
-          carx[i] = x;
-          cary[i] = y;
-        } else {
-          acc[i][j] = x;
-          if (two) acc[i][j + 1] = y;
-        }
-      }
-      // this pair's share of the load slots and of the B stores
-      int nvm = 0, nst = 0;
-      const int s0 = p * NLS / NP, s1 = (p + 1) * NLS / NP;
-#pragma unroll
-      for (int s = 0; s < NLS; ++s)
-        if (s >= s0 && s < s1) {
-          load_slot(s);
-          nvm += s < NAS ? AV : 1;
-        }
-      {
-        const int w0 = p * BPT / NP, w1 = (p + 1) * BPT / NP;
-#pragma unroll
-        for (int q = 0; q < BPT; ++q)
-          if (q >= w0 && q < w1) {
-            storeB1(xb, q, wb);
-            ++nst;
-          }
-        if (p == NP / 2) splitA(xa, afn, ksn);
-      }
-      constexpr int MQ = 4 * RF;  // a third of a pair's MFMAs
-      b3_sgb<0x100>(nrd);                                    // ds_read
-      if (two) b3_sgb<0x008>(MQ); else b3_sgb<0x008>(MQ / 2);  // MFMA
-      b3_sgb<0x020>(nvm);                                    // global load
-      if (two) b3_sgb<0x008>(MQ); else b3_sgb<0x008>(MQ / 2);
-      b3_sgb<0x200>(nst);                                    // ds_write
-      if (two) b3_sgb<0x008>(MQ); else b3_sgb<0x008>(MQ);
-    }
-    if constexpr (kB3StepAcc) {  // the last pair's step sums
-      constexpr int jl = 2 * (NP - 1);
-#pragma unroll
-      for (int i = 0; i < RF; ++i) {
-        acc[i][jl] += carx[i];
-        if constexpr (jl + 1 < NF) acc[i][jl + 1] += cary[i];
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-  };
-
-  // The last step (tail): no operand loads, B stores or A split are left to issue (the main
-  // steps fetch two steps ahead); for an addend epilogue it issues the addend loads in the load
-  // slots instead: the addend of fragment column j is loaded beside the MFMAs of pair j / 2, so
-  // its HBM traffic overlaps the matrix work instead of following it.  (A two-step tail that
-  // also splits A of the last step spilled 16-22 VGPRs on the gathered-A kernels.)
-  constexpr bool ADD = b3_ep_addend<EP>::value;
+  // The addend of an addend epilogue, in MFMA layout; the tail step loads it.  The lane
+  // coordinates of its loads are recomputed behind an opaque copy of the thread id: shared with
+  // the prologue's, they would stay live across the main loop (spills)
   float arow_v[ADD ? RF : 1][ADD ? NF : 1][4];
   float acol_v[ADD ? NF : 1];
-  // the lane coordinates of the addend loads are recomputed behind an opaque copy of the thread
-  // id: shared with the prologue's, they would stay live across the main loop (spills)
   int otid = 0;
   auto add_loads = [&](int j) {
     if constexpr (ADD) {
@@ -555,9 +426,38 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
           arow_v[i][j][r] = ep.add_row(m0 + (ow * RF + i) * 16 + ofg * 4 + r, col);
     }
   };
-  auto tstep = [&](int cb, const b3_u4 (&afc)[RF][3], const ARaw* xa, b3_u4 (&afn)[RF][3],
-                   int ksn, bool prefetch, bool last) {
+
+  // read-ahead depth: 4 fragment columns, 2 at 11 (4 spill the gathered-A kernels there)
+  constexpr int LDA = NF == 11 ? 2 : (4 < NF ? 4 : NF - 1);
+  constexpr int AV = (int)(sizeof(typename AL::Raw) / 16);  // VMEM instructions per A fetch unit
+  constexpr int NAS = RF * 2;                               // A fetch units per step
+  constexpr int NLS = NAS + BPT;                            // load slots per step
+  constexpr int NP = (NF + 1) / 2;                          // MFMA pairs per step
+  // One step: the MFMAs of step ks (LDS buffer cb, fragments afc), column groups in pairs, with
+  // the step's other work spread over them -- the vector-memory path and the matrix pipe overlap
+  // only when loads are interleaved with the MFMAs; issued as one burst per step they stall every
+  // wave of the workgroup at once.
+  //   A main step (kMain) stages: the global loads of the next raw set (A(ksa) -> ya,
+  // B(ksb) -> yb), the LDS stores of the current set's B block (xb -> buffer wb) and the split of
+  // its A fragments (xa -> afn, step ksn).
+  //   The last step (kTail) has none of it left (the main steps load two steps ahead) and ignores
+  // those arguments; for an addend epilogue it loads the addend instead, fragment column j beside
+  // the MFMAs of pair j / 2, so its HBM traffic overlaps the matrix work instead of following it.
+  // (A two-step tail that also splits A of the last step spilled 16-22 VGPRs on the gathered-A
+  // kernels.)
+  constexpr std::false_type kMain{};
+  constexpr std::true_type kTail{};
+  auto step = [&](auto TAILc, int cb, const b3_u4 (&afc)[RF][3], const BRaw& xb, int wb,
+                  const ARaw& xa, b3_u4 (&afn)[RF][3], int ksn, ARaw& ya, int ksa, BRaw& yb,
+                  int ksb) {
+    constexpr bool TAIL = decltype(TAILc)::value;
     const b3_u4* Bs = b3_lds + cb * BU4;
+    int kba = 0;
+    const b3_u4* bsrc = nullptr;
+    if constexpr (!TAIL) {
+      kba = ksa * B3_BK + 4 * fg;
+      bsrc = Bimg + (size_t)(ksb < nk ? ksb : nk - 1) * 3 * nimg * 4;
+    }
     constexpr int RING = LDA + 2;
     b3_u4 bq[RING][3];
     auto rd = [&](int j) {
@@ -568,8 +468,9 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
     };
 #pragma unroll
     for (int j = 0; j < LDA; ++j) rd(j);
-    if constexpr (kB3ReadAheadFence) __builtin_amdgcn_sched_barrier(0);
-    floatx4 carx[RF], cary[RF];  // kB3StepAcc: the previous pair's step sums
+    // the read-ahead is issued here, ahead of everything (else the scheduler fills each pair's
+    // ds_read group with that pair's own reads and waits on them right away)
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const int j = 2 * p;
@@ -583,64 +484,53 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
         rd(j + 1 + LDA);
         nrd += 3;
       }
-      const b3_u4(&b)[3] = bq[j % RING];
-      const b3_u4(&c)[3] = bq[(j + 1) % RING];
 #pragma unroll
-      for (int i = 0; i < RF; ++i) {
-        // kB3StepAcc: the step's six products into a zero accumulator, then one fp32 add into
-        // the running sum (the matrix core aligns every product of an MFMA to its largest
-        // operand, accumulator included: the small pieces' products would be rounded at the
-        // running sum's ulp, tools/diag/bf16_round_probe.hip).  The add of pair p is issued
-        // behind pair p + 1's MFMAs (carry): only two pairs' temporaries are live.
-        floatx4 x = kB3StepAcc ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[i][j];
-        floatx4 y = kB3StepAcc ? x : (two ? acc[i][j + 1] : x);
-        x = b3_mfma(afc[i][1], b[1], x);
-        if (two) y = b3_mfma(afc[i][1], c[1], y);
-        x = b3_mfma(afc[i][0], b[2], x);
-        if (two) y = b3_mfma(afc[i][0], c[2], y);
-        x = b3_mfma(afc[i][2], b[0], x);
-        if (two) y = b3_mfma(afc[i][2], c[0], y);
-        x = b3_mfma(afc[i][0], b[1], x);
-        if (two) y = b3_mfma(afc[i][0], c[1], y);
-        x = b3_mfma(afc[i][1], b[0], x);
-        if (two) y = b3_mfma(afc[i][1], c[0], y);
-        x = b3_mfma(afc[i][0], b[0], x);
-        if (two) y = b3_mfma(afc[i][0], c[0], y);
-        if constexpr (kB3StepAcc) {
-          if (p > 0) {
-            acc[i][j - 2] += carx[i];
-            acc[i][j - 1] += cary[i];  // the previous pair always has two columns
+      for (int i = 0; i < RF; ++i)
+        b3_mfma6x2(afc[i], bq[j % RING], bq[(j + 1) % RING], two, acc[i][j],
+                   acc[i][two ? j + 1 : j]);
+      constexpr int MQ = 4 * RF;  // a third of a pair's MFMAs
+      if constexpr (!TAIL) {
+        // this pair's share of the load slots and of the B stores
+        int nvm = 0, nst = 0;
+        const int s0 = p * NLS / NP, s1 = (p + 1) * NLS / NP;
+#pragma unroll
+        for (int s = 0; s < NLS; ++s)
+          if (s >= s0 && s < s1) {
+            if (s < NAS)
+              ya[s >> 1][s & 1] = al.fetch(arow[s >> 1], kba + 16 * (s & 1), K);
+            else
+              yb[s - NAS] = bsrc[boff[s - NAS]];
+            nvm += s < NAS ? AV : 1;
           }
-          carx[i] = x;
-          cary[i] = y;
-        } else {
-          acc[i][j] = x;
-          if (two) acc[i][j + 1] = y;
-        }
-      }
-      int nvm = 0;
-      if (ADD && prefetch) {
-        add_loads(j);
-        if (two) add_loads(j + 1);
-        nvm = (two ? 2 : 1) * 4 * RF;
-      }
-      if (xa && p == NP / 2) splitA(*xa, afn, ksn);
-      constexpr int MQ = 4 * RF;
-      b3_sgb<0x100>(nrd);
-      if (two) b3_sgb<0x008>(MQ); else b3_sgb<0x008>(MQ / 2);
-      b3_sgb<0x020>(nvm);
-      if (two) b3_sgb<0x008>(2 * MQ); else b3_sgb<0x008>(MQ + MQ / 2);
-    }
-    if constexpr (kB3StepAcc) {  // the last pair's step sums
-      constexpr int jl = 2 * (NP - 1);
+        const int w0 = p * BPT / NP, w1 = (p + 1) * BPT / NP;
 #pragma unroll
-      for (int i = 0; i < RF; ++i) {
-        acc[i][jl] += carx[i];
-        if constexpr (jl + 1 < NF) acc[i][jl + 1] += cary[i];
+        for (int q = 0; q < BPT; ++q)
+          if (q >= w0 && q < w1) {
+            storeB1(xb, q, wb);
+            ++nst;
+          }
+        if (p == NP / 2) splitA(xa, afn, ksn);
+        b3_sgb<0x100>(nrd);                                    // ds_read
+        if (two) b3_sgb<0x008>(MQ); else b3_sgb<0x008>(MQ / 2);  // MFMA
+        b3_sgb<0x020>(nvm);                                    // global load
+        if (two) b3_sgb<0x008>(MQ); else b3_sgb<0x008>(MQ / 2);
+        b3_sgb<0x200>(nst);                                    // ds_write
+        b3_sgb<0x008>(MQ);
+      } else {
+        int nvm = 0;
+        if constexpr (ADD) {
+          add_loads(j);
+          if (two) add_loads(j + 1);
+          nvm = (two ? 2 : 1) * 4 * RF;
+        }
+        b3_sgb<0x100>(nrd);
+        if (two) b3_sgb<0x008>(MQ); else b3_sgb<0x008>(MQ / 2);
+        b3_sgb<0x020>(nvm);
+        if (two) b3_sgb<0x008>(2 * MQ); else b3_sgb<0x008>(MQ + MQ / 2);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (last) __syncthreads();
+    __syncthreads();
   };
 
   {  // prologue: buffers 0, 1 <- B(0), B(1); afr0 <- A(0); raw set 0 <- A(1), B(2)
@@ -662,11 +552,11 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
     const int nmain = nk - 1;  // steps before the tail (the last step)
     for (int ks = 0; ks < nmain; ks += 2) {
       // even step: consume set 0 (A(ks+1), B(ks+2)), fill set 1 with A(ks+2), B(ks+3)
-      step(cb, afr0, xb0, cb == 0 ? 2 : cb - 1, xa0, afr1, ks + 1, xa1, ks + 2, xb1, ks + 3);
+      step(kMain, cb, afr0, xb0, cb == 0 ? 2 : cb - 1, xa0, afr1, ks + 1, xa1, ks + 2, xb1, ks + 3);
       cb = cb == 2 ? 0 : cb + 1;
       if (ks + 1 >= nmain) break;
       // odd step: consume set 1 (A(ks+2), B(ks+3)), fill set 0 with A(ks+3), B(ks+4)
-      step(cb, afr1, xb1, cb == 0 ? 2 : cb - 1, xa1, afr0, ks + 2, xa0, ks + 3, xb0, ks + 4);
+      step(kMain, cb, afr1, xb1, cb == 0 ? 2 : cb - 1, xa1, afr0, ks + 2, xa0, ks + 3, xb0, ks + 4);
       cb = cb == 2 ? 0 : cb + 1;
     }
     // tail: the last step uses fragment set nmain % 2 (split by the step before), moved into set
@@ -678,7 +568,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
         for (int q = 0; q < 3; ++q) afr0[i][q] = afr1[i][q];
     }
     if constexpr (ADD) asm volatile("v_mov_b32 %0, %1" : "=v"(otid) : "v"(tid));
-    tstep(cb, afr0, nullptr, afr1, 0, true, true);
+    step(kTail, cb, afr0, xb0, 0, xa0, afr1, 0, xa1, 0, xb1, 0);  // stages nothing: sets unused
   }
 
   CGR_STAMP(2);
@@ -699,7 +589,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
   if constexpr (!ADD) {
 #pragma unroll
     for (int it = 0; it < EP_IT; ++it) {
-      if constexpr (FLAT) {
+      if constexpr (TILE) {
         const int q = min(tid + NT * it, BM * C4 - 1);
         const int r = q / C4;
         pv[it] = ep.pre4(m0 + r, n0 + 4 * (q - r * C4));
@@ -721,7 +611,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
         smask[2 * (tid >> 6)] = (uint32_t)b;
         smask[2 * (tid >> 6) + 1] = (uint32_t)(b >> 32);
       }
-      if constexpr (SEG && FLAT) {
+      if constexpr (SEG) {
         // the segment-start rows of this wave's 64 rows (below the tile's row count), in order,
         // into half tid / 64 of the start list (the halves' counts come from smask)
         const bool real = sstart && tid < M - m0;
@@ -741,197 +631,150 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
   __syncthreads();
   CGR_STAMP(3);
   if constexpr (TILE) {
-    ep.template tile<BM, BN, NT, S::LDC, EP_IT, FLAT ? 0 : RPP>(pv, C, sd, m0, n0, tile, tid);
+    ep.template tile<BM, BN, NT, S::LDC, EP_IT>(pv, C, sd, m0, n0, tile, tid);
   } else {
-  // SEG && FLAT: the tile's segment starts, written before the barrier above in two halves
-  // (rows 0..63 from slist[0], rows 64..127 from slist[64]); nh0 / nseg from the mask
-  const int* slist = sd + BM + 2 + 16;
-  const int nrow_t = min(BM, M - m0);
-  uint64_t mlo = 0, mhi = 0;
-  int nseg = 0, nh0 = 0;
-  if constexpr (SEG && FLAT) {
-    mlo = smask[0] | ((uint64_t)smask[1] << 32);
-    mhi = smask[2] | ((uint64_t)smask[3] << 32);
-    // starts among rows < nrow_t (rows past the tile's count are sentinel starts)
-    const uint64_t klo = nrow_t >= 64 ? mlo : mlo & ((1ull << nrow_t) - 1);
-    const uint64_t khi = nrow_t >= 128 ? mhi : (nrow_t > 64 ? mhi & ((1ull << (nrow_t - 64)) - 1) : 0);
-    nh0 = __popcll(klo);
-    nseg = nh0 + __popcll(khi);
-  }
-  auto seg_start = [&](int j) { return slist[j < nh0 ? j : 64 + (j - nh0)]; };
-  // segment [r, e) x column group c4 of the tile: a[v] stored, or handed over (crossing)
-  auto seg_out = [&](int r, int e, int c4, float4 a) {
-    if constexpr (SEG) {
-      const int col = n0 + 4 * c4;
-      const int v = sd[r + 1];
-      float* dst = ep.aout + (int64_t)v * ep.lda + col;
-      const bool head = r == 0 && sd[0] == v, tail = e == nrow_t && sd[nrow_t + 1] == v;
-      if (tail && !head && ep.znext)  // the tile where a crossing segment starts
-        *reinterpret_cast<float4*>(ep.znext + (int64_t)v * ep.lda + col) = f4zero();
-      if (head || tail) {
-        const int b = ep.dst_ptr[v], ee = ep.dst_ptr[v + 1];
-        if (seg_tiles(b, ee, BM) <= 2) {
-          atomicAdd(dst, a.x);
-          atomicAdd(dst + 1, a.y);
-          atomicAdd(dst + 2, a.z);
-          atomicAdd(dst + 3, a.w);
-        } else {
-          sc1_store4(ep.part + ((int64_t)tile * 2 + slot_of(tm, b / BM)) * BN + 4 * c4, a);
-        }
-      } else {
-        st4_nt(dst, a);  // (common.hpp)
-      }
-    }
-  };
-  // SEG && FLAT && kB3SegMerge: ONE pass over (segment, column group) items -- each item applies
-  // its segment's rows in row order (h stored) and sums them: no h write-back to LDS, no second
-  // pass behind a barrier.  The lanes of a wave take consecutive column groups of one or two
-  // segments, so they run the same row count but at segment boundaries.
-  constexpr bool MERGE = SEG && FLAT && kB3SegMerge;
-  auto apply_pass = [&](auto Ac) {
-    constexpr int A = decltype(Ac)::value;
-    if constexpr (MERGE) {
-#pragma unroll
-      for (int it = 0; it < EITF; ++it) {
-        const int q = tid + NT * it;
-        if (q >= nseg * C4) break;
-        const int j = q / C4, c4 = q - j * C4, col = n0 + 4 * c4;
-        if (col >= ep.N) continue;
-        const int r = seg_start(j), e = seg_end(mlo, mhi, r);
-        float4 a = f4zero();
-        for (int k = r; k < e; ++k)
-          a = f4add(a, ep.template apply4z_h<A>(
-                           m0 + k, col, *reinterpret_cast<const float4*>(&C[k * S::LDC + 4 * c4]),
-                           cx));
-        seg_out(r, e, c4, a);
-      }
-    } else if constexpr (FLAT) {
-#pragma unroll
-      for (int it = 0; it < EP_IT; ++it) {
-        const int q = tid + NT * it;
-        if (q >= BM * C4) break;
-        const int r = q / C4, c4 = q - r * C4, col = n0 + 4 * c4;
-        float4* cp = reinterpret_cast<float4*>(&C[r * S::LDC + 4 * c4]);
-        if constexpr (SEG)
-          *cp = ep.template apply4z_h<A>(m0 + r, col, *cp, cx);  // keep h for the sums
-        else
-          ep.template apply4z<A>(m0 + r, col, *cp, cx);
-      }
-    } else {
-#pragma unroll
-      for (int it = 0; it < EIT; ++it) {
-        const int r = er0 + RPP * it;
-        if (eact && r < BM) {
-          float4* cp = reinterpret_cast<float4*>(&C[r * S::LDC + 4 * ec4]);
-          if constexpr (SEG && ADD)
-            *cp = ep.template apply4z_h<A>(m0 + r, ecol, *cp, cx);  // keep h for the sums
-          else if constexpr (SEG)
-            *cp = ep.template apply4p_h<A>(m0 + r, ecol, *cp, pv[it], cx);
-          else if constexpr (ADD)
-            ep.template apply4z<A>(m0 + r, ecol, *cp, cx);
-          else if constexpr (b3_ep_act<EP>::value)
-            ep.template apply4p<A>(m0 + r, ecol, *cp, pv[it], cx);
-          else
-            ep.apply4p(m0 + r, ecol, *cp, pv[it], cx);
-        }
-      }
-    }
-  };
-  if constexpr (b3_ep_act<EP>::value) {  // one loop per activation, chosen once
-    if (ep.act == ACT_RELU) apply_pass(std::integral_constant<int, ACT_RELU>{});
-    else if (ep.act == ACT_SILU) apply_pass(std::integral_constant<int, ACT_SILU>{});
-    else apply_pass(std::integral_constant<int, -1>{});  // GELU and the rest
-  } else {
-    apply_pass(std::integral_constant<int, -1>{});
-  }
-  CGR_STAMP(4);
-  if constexpr (SEG) {
-    // a[v] = sum_{dst(i) = v} h[i] for the tile's columns (GNN.py:134): the thread owning the
-    // first row of a segment in the tile sums its rows in row order (the segment bounds from the
-    // tile's segment-start mask).  A segment inside the tile is stored; one crossing into one
+    // SEG: a[v] = sum_{dst(i) = v} h[i] for the tile's columns (GNN.py:134), each segment's rows
+    // summed in row order.  A segment inside the tile is stored; one crossing into one
     // neighbouring tile is added atomically to a[v], which edge_init_segsum_fwd zeroed (two
     // partials onto zero: p + q == q + p, deterministic); one over three or more row tiles (a hub
     // node, in-degree > BM + 1) leaves its partial in a slot fixed by the data and its last
     // contributor sums the slots in row-tile order -- deterministic for every in-degree.
-    const int nrow = nrow_t;
-    // segment [r, e) x column group c4 from the applied h rows in LDS
-    auto seg_item = [&](int r, int e, int c4) {
-      float4 a = f4zero();
-      for (int k = r; k < e; ++k)
-        a = f4add(a, *reinterpret_cast<const float4*>(&C[k * S::LDC + 4 * c4]));
-      seg_out(r, e, c4, a);
-    };
-    if constexpr (MERGE) {
-      // done by the apply pass
-    } else if constexpr (FLAT) {
-      __syncthreads();
-      // items (segment j, column group c4) of the compact segment list: no lane waits on a
-      // row that does not start a segment
-#pragma unroll
-      for (int it = 0; it < EITF; ++it) {
-        const int q = tid + NT * it;
-        if (q >= nseg * C4) break;
-        const int j = q / C4, c4 = q - j * C4;
-        if (n0 + 4 * c4 >= ep.N) continue;
-        const int r = seg_start(j);
-        seg_item(r, seg_end(mlo, mhi, r), c4);
-      }
-    } else {
-      __syncthreads();
+    // The tile's segment starts were written before the barrier above in two halves (rows 0..63
+    // from slist[0], rows 64..127 from slist[64]); nh0 / nseg from the mask
+    const int* slist = sd + BM + 2 + 16;
+    const int nrow_t = min(BM, M - m0);
+    uint64_t mlo = 0, mhi = 0;
+    int nseg = 0, nh0 = 0;
+    if constexpr (SEG) {
       mlo = smask[0] | ((uint64_t)smask[1] << 32);
       mhi = smask[2] | ((uint64_t)smask[3] << 32);
-#pragma unroll
-      for (int it = 0; it < EIT; ++it) {
-        const int r = er0 + RPP * it;
-        if (!eact || r >= nrow || ecol >= ep.N || !seg_bit(mlo, mhi, r)) continue;
-        seg_item(r, seg_end(mlo, mhi, r), ec4);
-      }
+      // starts among rows < nrow_t (rows past the tile's count are sentinel starts)
+      const uint64_t klo = nrow_t >= 64 ? mlo : mlo & ((1ull << nrow_t) - 1);
+      const uint64_t khi =
+          nrow_t >= 128 ? mhi : (nrow_t > 64 ? mhi & ((1ull << (nrow_t - 64)) - 1) : 0);
+      nh0 = __popcll(klo);
+      nseg = nh0 + __popcll(khi);
     }
-    // hub segments: the last contributor sums the slots of every row tile in order
-    const int vh = sd[0] == sd[1] ? sd[0] : -3;               // head segment's node, if any
-    const int vt = sd[nrow] == sd[nrow + 1] ? sd[nrow] : -3;  // tail segment's node, if any
-    auto hub = [&](int v) {
-      return v >= 0 && seg_tiles(ep.dst_ptr[v], ep.dst_ptr[v + 1], BM) >= 3;
+    auto seg_start = [&](int j) { return slist[j < nh0 ? j : 64 + (j - nh0)]; };
+    // segment [r, e) x column group c4 of the tile: a[v] stored, or handed over (crossing)
+    auto seg_out = [&](int r, int e, int c4, float4 a) {
+      if constexpr (SEG) {
+        const int col = n0 + 4 * c4;
+        const int v = sd[r + 1];
+        float* dst = ep.aout + (int64_t)v * ep.lda + col;
+        const bool head = r == 0 && sd[0] == v, tail = e == nrow_t && sd[nrow_t + 1] == v;
+        if (tail && !head && ep.znext)  // the tile where a crossing segment starts
+          *reinterpret_cast<float4*>(ep.znext + (int64_t)v * ep.lda + col) = f4zero();
+        if (head || tail) {
+          const int b = ep.dst_ptr[v], ee = ep.dst_ptr[v + 1];
+          if (seg_tiles(b, ee, BM) <= 2) {
+            atomicAdd(dst, a.x);
+            atomicAdd(dst + 1, a.y);
+            atomicAdd(dst + 2, a.z);
+            atomicAdd(dst + 3, a.w);
+          } else {
+            sc1_store4(ep.part + ((int64_t)tile * 2 + slot_of(tm, b / BM)) * BN + 4 * c4, a);
+          }
+        } else {
+          st4_nt(dst, a);  // (common.hpp)
+        }
+      }
     };
-    const bool bh = hub(vh), bt = vt != vh && hub(vt);  // uniform over the workgroup
-    if (bh || bt) {
-      int* scratch = sd + BM + 2;  // 16 words (B3NtShape::EPI_BYTES)
-      ep_vm_drain();  // this wave's slot stores
-      __syncthreads();
-      if (tid == 0) {
+    auto apply_pass = [&](auto Ac) {
+      if constexpr (SEG) {
+        // ONE pass over (segment, column group) items -- each item applies its segment's rows in
+        // row order (h stored) and sums them: no h write-back to LDS, no second pass behind a
+        // barrier.  The lanes of a wave take consecutive column groups of one or two segments, so
+        // they run the same row count but at segment boundaries.
+#pragma unroll
+        for (int it = 0; it < EITF; ++it) {
+          const int q = tid + NT * it;
+          if (q >= nseg * C4) break;
+          const int j = q / C4, c4 = q - j * C4, col = n0 + 4 * c4;
+          if (col >= ep.N) continue;
+          const int r = seg_start(j), e = seg_end(mlo, mhi, r);
+          float4 a = f4zero();
+          for (int k = r; k < e; ++k)
+            a = f4add(a, ep.template apply4z_h<decltype(Ac)::value>(
+                             m0 + k, col,
+                             *reinterpret_cast<const float4*>(&C[k * S::LDC + 4 * c4]), cx));
+          seg_out(r, e, c4, a);
+        }
+      } else if constexpr (ADD) {  // flat
+#pragma unroll
+        for (int it = 0; it < EP_IT; ++it) {
+          const int q = tid + NT * it;
+          if (q >= BM * C4) break;
+          const int r = q / C4, c4 = q - r * C4, col = n0 + 4 * c4;
+          const float4* cp = reinterpret_cast<const float4*>(&C[r * S::LDC + 4 * c4]);
+          ep.template apply4z<decltype(Ac)::value>(m0 + r, col, *cp, cx);
+        }
+      } else {  // this thread's column group
+#pragma unroll
+        for (int it = 0; it < EIT; ++it) {
+          const int r = er0 + RPP * it;
+          if (eact && r < BM) {
+            const float4* cp = reinterpret_cast<const float4*>(&C[r * S::LDC + 4 * ec4]);
+            ep.apply4p(m0 + r, ecol, *cp, pv[it], cx);
+          }
+        }
+      }
+    };
+    if constexpr (b3_ep_act<EP>::value) {  // one loop per activation, chosen once
+      if (ep.act == ACT_RELU) apply_pass(std::integral_constant<int, ACT_RELU>{});
+      else if (ep.act == ACT_SILU) apply_pass(std::integral_constant<int, ACT_SILU>{});
+      else apply_pass(std::integral_constant<int, -1>{});  // GELU and the rest
+    } else {
+      apply_pass(std::integral_constant<int, -1>{});
+    }
+    CGR_STAMP(4);
+    if constexpr (SEG) {
+      // hub segments: the last contributor sums the slots of every row tile in order
+      const int vh = sd[0] == sd[1] ? sd[0] : -3;  // head segment's node, if any
+      const int vt = sd[nrow_t] == sd[nrow_t + 1] ? sd[nrow_t] : -3;  // tail segment's node
+      auto hub = [&](int v) {
+        return v >= 0 && seg_tiles(ep.dst_ptr[v], ep.dst_ptr[v + 1], BM) >= 3;
+      };
+      const bool bh = hub(vh), bt = vt != vh && hub(vt);  // uniform over the workgroup
+      if (bh || bt) {
+        int* scratch = sd + BM + 2;  // 16 words (B3NtShape::EPI_BYTES)
+        ep_vm_drain();  // this wave's slot stores
+        __syncthreads();
+        if (tid == 0) {
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            const int v = k == 0 ? (bh ? vh : -3) : (bt ? vt : -3);
+            int done = 0;
+            if (v >= 0) {
+              const int cnt = seg_tiles(ep.dst_ptr[v], ep.dst_ptr[v + 1], BM);
+              done = __hip_atomic_fetch_add(&ep.cnt[(int64_t)v * ep.tiles_n + tn], 1,
+                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == cnt - 1;
+            }
+            scratch[14 + k] = done ? v : -1;
+          }
+        }
+        __syncthreads();
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-          const int v = k == 0 ? (bh ? vh : -3) : (bt ? vt : -3);
-          int done = 0;
-          if (v >= 0) {
-            const int cnt = seg_tiles(ep.dst_ptr[v], ep.dst_ptr[v + 1], BM);
-            done = __hip_atomic_fetch_add(&ep.cnt[(int64_t)v * ep.tiles_n + tn], 1,
-                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == cnt - 1;
+          const int v = scratch[14 + k];
+          if (v < 0) continue;
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // loads stay below the ticket
+          const int t0 = ep.dst_ptr[v] / BM, t1 = (ep.dst_ptr[v + 1] - 1) / BM;
+          for (int c4 = tid; c4 < C4; c4 += NT) {
+            const int col = n0 + 4 * c4;
+            if (col >= ep.N) continue;
+            float4 a = f4zero();
+            for (int t = t0; t <= t1; ++t)
+              a = f4add(a, sc1_load4(ep.part +
+                                     ((int64_t)(t * tiles_n + tn) * 2 + slot_of(t, t0)) * BN +
+                                     4 * c4));
+            *reinterpret_cast<float4*>(ep.aout + (int64_t)v * ep.lda + col) = a;
           }
-          scratch[14 + k] = done ? v : -1;
+          if (tid == 0) ep.cnt[(int64_t)v * ep.tiles_n + tn] = 0;
         }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int v = scratch[14 + k];
-        if (v < 0) continue;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // loads stay below the ticket
-        const int t0 = ep.dst_ptr[v] / BM, t1 = (ep.dst_ptr[v + 1] - 1) / BM;
-        for (int c4 = tid; c4 < C4; c4 += NT) {
-          const int col = n0 + 4 * c4;
-          if (col >= ep.N) continue;
-          float4 a = f4zero();
-          for (int t = t0; t <= t1; ++t)
-            a = f4add(a, sc1_load4(ep.part + ((int64_t)(t * tiles_n + tn) * 2 + slot_of(t, t0)) *
-                                                 BN + 4 * c4));
-          *reinterpret_cast<float4*>(ep.aout + (int64_t)v * ep.lda + col) = a;
-        }
-        if (tid == 0) ep.cnt[(int64_t)v * ep.tiles_n + tn] = 0;
       }
     }
   }
-  }  // !TILE
   CGR_STAMP_END((TILE ? 2 : 0) | (SEG ? 1 : 0) | (NF << 2) | (WAVES << 7));
 }
 

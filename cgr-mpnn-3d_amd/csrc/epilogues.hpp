@@ -251,15 +251,17 @@ struct EpSplit2 {
     if (r >= M || c >= 2 * H) return;
     if (c + 4 <= H) {
       *reinterpret_cast<float4*>(P + (int64_t)r * ld + c) = v;
-    } else if (c >= H) {
+    } else if (c >= H && c - H + 4 <= ld) {
       *reinterpret_cast<float4*>(Q + (int64_t)r * ld + (c - H)) = v;  // padding cols don't-care
-    } else {  // straddles H (H % 4 != 0)
+    } else {  // straddles H (H % 4 != 0), or Q's row end: at H % 4 == 3 the last group of a row
+              // starts at Q column ld - 3, and its fourth element would land on the next row's
+              // column 0 (past the buffer for the last row), racing that row's own store
       const float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int cc = c + k;
         if (cc < H) P[(int64_t)r * ld + cc] = e[k];
-        else if (cc < 2 * H) Q[(int64_t)r * ld + (cc - H)] = e[k];
+        else if (cc - H < ld) Q[(int64_t)r * ld + (cc - H)] = e[k];
       }
     }
   }

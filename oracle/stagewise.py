@@ -686,3 +686,86 @@ def judge(rec, params, cfg, ops_ref=F32):
         out.append(dict(stage=name, rho=r, rho_ref=rr, bar=bar(rr) + extra, argmax=list(at),
                         rho_fp64=r64))
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# the standalone DMPNNConv (csrc/conv.hip), in the caller's edge order
+# ----------------------------------------------------------------------------------------------
+# A conv record: edge_index [2, E] (reverse-edge pairs 2k, 2k + 1), N, h [E, H], weight [H, H],
+# bias [H], inv_deg (None: add; 1 / max(in-degree, 1) under mean), grad_a [N, H] / grad_out [E, H]
+# (None: the ABI's NULL), and what the implementation produced: a, out, grad_h, grad_weight,
+# grad_bias.
+def conv_dh(grad_out, grad_a, w, src, dst, rev, N, inv_deg=None, ops=REF):
+    """grad_h = (segsum_src(grad_out W) + grad_a)[dst] * inv_deg - (grad_out W)[rev]: layer_dh
+    extended by the grad_a term; a None gradient drops its terms."""
+    E = np.shape(dst)[0]
+    if grad_out is None:
+        z = np.zeros((E, np.shape(w)[1]))
+        st = Stage(ops.arr(z), z, 0.0)
+    else:
+        st = layer_dh(grad_out, w, src, dst, rev, N, inv_deg, ops)
+    if grad_a is None:
+        return st
+    t, St = ops.arr(grad_a)[dst], _abs(grad_a)[dst]
+    if inv_deg is not None:
+        t = t * ops.arr(inv_deg)[dst][:, None]
+        St = St * _abs(inv_deg)[dst][:, None]
+    return Stage(st.ref + t, _f8(st.S) + St, 0.0)
+
+
+def conv_stages(rec, ops=REF):
+    """Yield (name, got, stage) for the five stages of a conv record, each evaluated by ``ops``
+    from the record's own inputs to it (``out`` and ``grad_weight`` from the record's ``a``)."""
+    ei = np.asarray(rec["edge_index"], np.int64)
+    src, dst = ei[0], ei[1]
+    E, N = src.shape[0], int(rec["N"])
+    rev = np.arange(E) ^ 1
+    h, w, inv_deg = rec["h"], rec["weight"], rec.get("inv_deg")
+    H = np.shape(w)[0]
+    yield "a", rec["a"], aggregate(h, dst, N, inv_deg, ops)
+    yield "out", rec["out"], layer_pre(rec["a"], h, h, src, rev, w, rec["bias"], 0.0, ops)
+    go, ga = rec.get("grad_out"), rec.get("grad_a")
+    if go is None:  # exactly zero: any non-zero element is an infinite rho
+        yield "grad_weight", rec["grad_weight"], Stage(np.zeros((H, H), ops.dtype), 0.0, 0.0)
+        yield "grad_bias", rec["grad_bias"], Stage(np.zeros(H, ops.dtype), 0.0, 0.0)
+    else:
+        yield "grad_weight", rec["grad_weight"], tn(go, message(rec["a"], h, src, rev, ops), ops)
+        yield "grad_bias", rec["grad_bias"], colsum(go, ops)
+    yield "grad_h", rec["grad_h"], conv_dh(go, ga, w, src, dst, rev, N, inv_deg, ops)
+
+
+def conv_chain(edge_index, N, h, weight, bias, grad_a=None, grad_out=None, mean=False, ops=REF,
+               hooks=None):
+    """A conv record produced by the stage functions evaluated by ``ops`` (REF: the oracle itself;
+    F32: a stand-in kernel).  ``hooks`` {stage name: f(value, record so far) -> value} replace a
+    stage's output before anything reads it."""
+    hooks = hooks or {}
+    ei = np.asarray(edge_index, np.int64)
+    rec = dict(edge_index=ei, N=int(N), h=ops.arr(h), weight=ops.arr(weight), bias=ops.arr(bias),
+               inv_deg=None, grad_a=None if grad_a is None else ops.arr(grad_a),
+               grad_out=None if grad_out is None else ops.arr(grad_out),
+               a=None, out=None, grad_h=None, grad_weight=None, grad_bias=None)
+    if mean:
+        rec["inv_deg"] = ops.arr(1.0 / np.maximum(np.bincount(ei[1], minlength=N)[:N], 1))
+    gen = conv_stages(rec, ops)
+    for name, _, st in gen:  # each stage is evaluated only after its inputs are in the record
+        rec[name] = hooks[name](st.ref, rec) if name in hooks else st.ref
+    return rec
+
+
+def conv_judge(rec, ops_ref=F32):
+    """judge() for a conv record: [{stage, rho, rho_ref, bar, argmax, rho_fp64}]."""
+    out = []
+    for (name, got, st), (_, _, st32) in zip(conv_stages(rec, REF), conv_stages(rec, ops_ref)):
+        r, at = rho(got, st)
+        rr, _ = rho(st32.ref, st)
+        out.append(dict(stage=name, rho=r, rho_ref=rr, bar=bar(rr), argmax=list(at), rho_fp64=r))
+    return out
+
+
+def segsum_judge(got, vals, index, nseg, ops_ref=F32):
+    """One row for a bare segment sum (cgr_segment_sum): out[index[j]] += vals[j]."""
+    st = aggregate(vals, index, nseg)
+    r, at = rho(got, st)
+    rr, _ = rho(aggregate(vals, index, nseg, ops=ops_ref).ref, st)
+    return dict(stage="segment_sum", rho=r, rho_ref=rr, bar=bar(rr), argmax=list(at), rho_fp64=r)

@@ -101,3 +101,59 @@ def write_report(case, rows):
                                                ("stage", "rho", "rho_ref", "bar", "argmax",
                                                 "rho_fp64")}))
     _write_report("stage_errors.json", STAGE_ERRORS)
+
+
+# ---------------------------------------------------------------------------------------------
+# the standalone DMPNNConv's cases, shared by tests/test_gpu_conv_stagewise.py (the kernels) and
+# tests/test_stagewise_refs.py (the fp32 stand-in at the same shapes)
+# ---------------------------------------------------------------------------------------------
+def conv_graph(name):
+    """(edge_index [2, E] int64 in reverse-edge pairs, N)."""
+    from test_gpu_parity import _hub_batch, _sparse_batch
+
+    from cgr_mpnn_3D._amd.synth import make_batch
+
+    if name == "e322":  # N 147, E 322: a partial last 64-row tile, a last split-K split of 2 rows
+        b = make_batch(7, 21, 23, n_mace=40, seed=112)
+    elif name == "hub":  # E 1056: dst segments of 150 / 70 / 300 rows, 17 split-K slabs
+        b = _hub_batch([150, 3, 70, 300, 5], seed=43)
+    elif name == "sparse":  # N 240, E 48: most nodes have in-degree 0
+        b = _sparse_batch(6, 40, seed=31)
+    else:
+        raise KeyError(name)
+    return np.ascontiguousarray(b.edge_index, dtype=np.int64), int(b.x.shape[0])
+
+
+# name: (graph, H, mean aggregation, grad_a given, grad_out given)
+CONV_CASES = {
+    "h80_both": ("e322", 80, False, True, True),  # NT RN = 5, TN (5, 5), one column tile
+    "h80_no_grad_a": ("e322", 80, False, False, True),
+    "h80_no_grad_out": ("e322", 80, False, True, False),
+    "h160": ("e322", 160, False, True, True),  # two 80-wide tiles each way
+    "h100": ("e322", 100, False, True, True),  # RN = 4, a ragged second tile
+    "h45_both": ("e322", 45, False, True, True),  # VEC 1, Hp 48
+    "h45_no_grad_a": ("e322", 45, False, False, True),
+    "h45_no_grad_out": ("e322", 45, False, True, False),
+    "h30": ("e322", 30, False, True, True),  # the VEC = 2 weight loader
+    "h12": ("e322", 12, False, True, True),  # Kout <= 16: TN RN = 1
+    "h528": ("e322", 528, False, True, True),  # above 512: several tiles each way
+    "hub_h160": ("hub", 160, False, True, True),
+    "sparse_mean_h45": ("sparse", 45, True, True, True),  # in-degree 0: inv_deg = 1
+}
+
+
+def conv_inputs(case):
+    """The case's inputs as fp32 numpy: dict(edge_index, N, h, weight, bias, grad_a, grad_out,
+    mean); a gradient the case leaves out is None."""
+    import zlib
+
+    graph, H, mean, with_ga, with_go = CONV_CASES[case]
+    ei, N = conv_graph(graph)
+    E = ei.shape[1]
+    rng = np.random.default_rng(zlib.crc32(case.encode()))
+    k = 1.0 / np.sqrt(H)
+    f4 = lambda a: np.ascontiguousarray(a, np.float32)  # noqa: E731
+    return dict(edge_index=ei, N=N, mean=mean, h=f4(rng.standard_normal((E, H))),
+                weight=f4(rng.uniform(-k, k, (H, H))), bias=f4(rng.uniform(-k, k, H)),
+                grad_a=f4(rng.standard_normal((N, H))) if with_ga else None,
+                grad_out=f4(rng.standard_normal((E, H))) if with_go else None)

@@ -17,8 +17,9 @@ allowance u (8 + |z|)(1 + |z|) (x |upstream gradient| for a derivative).  DESIGN
 the bars and records the measured rho per stage (stage_errors.json of this file's run).
 
 Every case also asserts that a second run on the same inputs reproduces every stage buffer bit
-for bit, and which weight-gradient family (split-bf16 e-image TN, or an fp32 TN) produced the
-gradients, from the library's per-class profile of a third run.
+for bit, and which weight-gradient kernel family (split-bf16 e-image TN, the register-direct fp32
+TN or the LDS-staged fp32 TN) produced each class of gradients, from the library's per-class
+profile of a third run.
 """
 
 import numpy as np
@@ -93,7 +94,9 @@ def _flat(rec):
 
 
 def _tn_families(cfg_t, data, B, params, dy, dropout_ps, training):
-    """{"readout" | "layer" | "node": "b3" | "f32"} from the per-class profile of one run."""
+    """{"readout" | "layer" | "node": "b3" | "tnr" | "f32"} from the per-class profile of one run:
+    the split-bf16 e-image TN (plain class name), the register-direct fp32 TN ("[tnr]") or the
+    LDS-staged fp32 TN ("[f32]")."""
     lib = native.load()
     lib.cgr_profile_reset()
     lib.cgr_profile_enable(1)
@@ -107,7 +110,7 @@ def _tn_families(cfg_t, data, B, params, dy, dropout_ps, training):
     for k, c in TN_CLASSES.items():
         forms = [s for s in ("", "[tnr]", "[f32]") if c + s in classes]
         assert len(forms) == 1, (c, sorted(classes))
-        fam[k] = "b3" if forms[0] == "" else "f32"
+        fam[k] = {"": "b3", "[tnr]": "tnr", "[f32]": "f32"}[forms[0]]
     return fam, classes
 
 
@@ -144,9 +147,11 @@ def _stagewise(case, b, H, D, act, skip, dev, *, inputs=False, aggr="add", pool=
                  B)
     for (k, v), (_, v2) in zip(_flat(rec), _flat(rec2)):
         assert v.tobytes() == v2.tobytes(), f"{case}: {k} differs between two runs"
-    rec["tn"], classes = _tn_families(cfg_t, data, B, params, dy, dps, training)
+    fam, classes = _tn_families(cfg_t, data, B, params, dy, dps, training)
     if expect_tn is not None:
-        assert rec["tn"] == expect_tn, (rec["tn"], sorted(classes))
+        assert fam == expect_tn, (fam, sorted(classes))
+    # the oracle judges two arithmetics: split-bf16, and fp32 (both fp32 kernel families)
+    rec["tn"] = {k: "b3" if f == "b3" else "f32" for k, f in fam.items()}
 
     rec["x"], rec["dy"] = x, _np(dy)
     deg = np.bincount(rec["dst_s"], minlength=N)[:N]
@@ -175,6 +180,7 @@ def _stagewise(case, b, H, D, act, skip, dev, *, inputs=False, aggr="add", pool=
 
 B3 = dict(readout="b3", layer="b3", node="b3")
 F32 = dict(readout="f32", layer="f32", node="f32")
+TNR = dict(readout="tnr", layer="tnr", node="tnr")
 
 
 def test_case01_every_stage_with_stored_pre(cuda_device):
@@ -189,6 +195,15 @@ def test_case02_odd_widths(cuda_device):
     # F = 85 (odd), H = 37 (Hp = 40): masked loaders, padded rows, 3 column fragments
     b = make_batch(6, 14, 16, n_mace=7, seed=102)
     _stagewise("c02_gelu_h37", b, 37, 2, "gelu", True, cuda_device, inputs=True, expect_tn=B3)
+
+
+def test_case02_width_3_mod_4(cuda_device):
+    # H = 39 (Hp = 40): the merged x-GEMM's last float4 column group of a Q row starts at column
+    # Hp - 3; its fourth element belongs to no row (EpSplit2: it used to land on the next row's
+    # Q[., 0], racing that row's own store across two 64-row tiles)
+    b = make_batch(6, 14, 16, n_mace=7, seed=102)
+    assert b.x.shape[0] > 64
+    _stagewise("c02_gelu_h39", b, 39, 2, "gelu", True, cuda_device, inputs=True, expect_tn=B3)
 
 
 def test_case03_relu_unpadded_x(cuda_device):
@@ -207,9 +222,11 @@ def test_case04_cfg2_widths(cuda_device):
 
 def test_case05_wider_than_512(cuda_device):
     # H = 528 > 512: the unfused edge init / layer forward + segment_sum launches, every weight
-    # gradient on an fp32 TN family (33 fragments do not fit the e-image TN)
+    # gradient on an fp32 TN family (33 fragments do not fit the e-image TN): H % 4 == 0 puts the
+    # layer on tnr<4, 4>, H % 5 != 0 the x-side two on the LDS-staged TN
     b = make_batch(8, n_atoms=20, n_bonds=22, n_mace=16, seed=105)
-    _stagewise("c05_silu_h528", b, 528, 2, "silu", False, cuda_device, inputs=True, expect_tn=F32)
+    _stagewise("c05_silu_h528", b, 528, 2, "silu", False, cuda_device, inputs=True,
+               expect_tn=dict(layer="tnr", readout="f32", node="f32"))
 
 
 @pytest.mark.parametrize("skip", [True, False])
@@ -263,3 +280,88 @@ def test_case11_train_mode_dropout(cuda_device):
     # case 1 in train mode, p = 0.02: forward and dpre stages with the GPU's own recovered mask
     b = make_batch(12, n_atoms=30, n_bonds=34, n_mace=40, seed=101)
     _stagewise("c11_dropout", b, 128, 3, "silu", True, cuda_device, p_drop=0.02, expect_tn=B3)
+
+
+# ---------------------------------------------------------------------------------------------
+# H > 512: edge_init_fwd + segment_sum, a plain EpLayer launch + segment_sum per layer, every
+# weight gradient on one of the fp32 TN kernels, chosen in gnn_bwd.hip from divisibility:
+#   layer    tnr<5, 5> (H % 5 == 0), else tnr<4, 4> (H % 4 == 0), else the LDS-staged tn_gemm
+#   readout  tnr<5, 4> over [x | a_D] when H % 5 == 0 and (Fp + H) % 4 == 0, else tn_gemm
+#   node     tnr<5, 4> when H % 5 == 0 (x columns padded to Fp, or F % 4 == 0), else tn_gemm
+# The batches have E = 2 (mod 4) and an odd N unless said otherwise: the tnr waves' last 4-row
+# step and the last split-K split are partial.
+# ---------------------------------------------------------------------------------------------
+def _wide_batch(n_mace, seed, graphs=7):
+    return make_batch(graphs, 21, 23, n_mace=n_mace, seed=seed)
+
+
+def test_case12_sweep_width(cuda_device):
+    # H = 1000, the reference sweep's width: 13 column tiles of tnr<5, 5>, F = 118 -> Fp = 120
+    b = _wide_batch(40, 112)
+    assert (b.x.shape[0], b.edge_index.shape[1], b.x.shape[1]) == (147, 322, 118)
+    _stagewise("c12_silu_h1000", b, 1000, 2, "silu", True, cuda_device, inputs=True,
+               expect_tn=TNR)
+
+
+def test_case13_mixed_families_padded_width(cuda_device):
+    # H = 515 (Hp = 516), F = 85 -> Fp = 88: H % 5 == 0 but (Fp + H) % 4 != 0, so the readout
+    # runs tn_gemm and the other two tnr within one backward; the layer TN's 6 splits of 64 rows
+    # over E = 322 leave 2 rows to the last
+    b = _wide_batch(7, 113)
+    assert (b.edge_index.shape[1], b.x.shape[1]) == (322, 85)
+    _stagewise("c13_gelu_h515", b, 515, 2, "gelu", True, cuda_device, inputs=True,
+               expect_tn=dict(layer="tnr", readout="f32", node="tnr"))
+
+
+def test_case14_prime_width_relu_x_in_place(cuda_device):
+    # H = 521 (prime): every weight gradient on tn_gemm; F = 80: x read in place; ReLU
+    b = _wide_batch(2, 114)
+    assert b.x.shape[1] == 80
+    _stagewise("c14_relu_h521", b, 521, 3, "relu", False, cuda_device, inputs=True, expect_tn=F32)
+
+
+def test_case15_hub_segments_three_column_tiles(cuda_device):
+    # hub segments of 150 / 70 / 300 rows across row tiles, H = 520; F = 21 -> Fp = 24: one
+    # ragged k tile in the node TN
+    b = _hub_batch([150, 3, 70, 300, 5], seed=43)
+    assert b.edge_index.shape[1] == 1056
+    _stagewise("c15_hub_h520", b, 520, 2, "relu", True, cuda_device, expect_tn=TNR)
+
+
+def test_case16_mean_modes_isolated_nodes_dropout(cuda_device):
+    # mean / mean with in-degree-0 nodes (scale_rows after the unfused segment_sum) and dropout
+    # in the unfused forward; H = 516: tnr<4, 4> for the layer
+    b = _sparse_batch(6, 40, seed=31)
+    _stagewise("c16_mean_h516", b, 516, 2, "silu", True, cuda_device, aggr="mean", pool="mean",
+               p_drop=0.02, expect_tn=dict(layer="tnr", readout="f32", node="f32"))
+
+
+def test_case17_unpaired_order_unpadded_x_tnr(cuda_device):
+    # edges shuffled inside every graph with the unfused forward; F = 80, H = 560: the tnr
+    # branches that read b->x directly
+    u = _shuffled_pairs(_wide_batch(2, 115, graphs=6), seed=5)
+    assert u.x.shape[1] == 80
+    _stagewise("c17_unpaired_h560", u, 560, 2, "gelu", True, cuda_device, expect_tn=TNR)
+    torch.cuda.synchronize()
+    bits = native.raise_device_errors(cuda_device)  # raises on a completion timeout
+    assert bits & native.DEVERR_UNPAIRED_SEEN
+
+
+def test_predict_rings_equal_training_forward_bitwise_h1000(cuda_device):
+    # case 12's widths at depth 4: the no-grad forward (cgr_gnn_predict: h on a two-buffer ring,
+    # a on a three-buffer ring, no fused zeroing above 512) against the grad-enabled forward
+    b = _wide_batch(40, 112)
+    data = b.to_torch(cuda_device)
+    torch.manual_seed(4 * 7 + 1000)
+    m = GNN(b.x.shape[1], b.edge_attr.shape[1], depth=4, hidden_sizes=[1000] * 4,
+            dropout_ps=[0.0] * 4, activation_fn=ACT["silu"], use_learnable_skip=True)
+    with torch.no_grad():
+        for i, w in enumerate(m.skip_weights):
+            w.fill_(0.5 + 0.25 * i)
+    m = m.to(cuda_device).eval()
+    y_train = m(data)  # grad enabled, parameters require grad: the training forward
+    assert y_train.requires_grad
+    with torch.no_grad():
+        y_pred = m(data)
+    assert not y_pred.requires_grad
+    assert torch.equal(y_pred, y_train.detach())

@@ -8,7 +8,10 @@ bars are attainable by an honest fp32 implementation and are missed by a subtly 
   the HIP kernels to, at that file's shapes;
 * the activation allowance tol_act holds for torch fp32 over |z| from 1e-30 to 250;
 * sensitivity: four one-element kernel bugs each exceed their stage's bar -- and only that
-  stage's -- while one of them passes the end-to-end bars of tests/test_gpu_parity.py.
+  stage's -- while one of them passes the end-to-end bars of tests/test_gpu_parity.py;
+* the same three for the standalone DMPNNConv's stages (conv_stages): torch float64 autograd of
+  the reference conv to 1e-12, the fp32 stand-in at tests/test_gpu_conv_stagewise.py's shapes,
+  and one-element bugs that exceed their own stage's bar only.
 """
 
 import numpy as np
@@ -16,7 +19,8 @@ import pytest
 import torch
 
 from conftest import ACT_NAMES
-from stagewise_common import TORCH_F32, _ACT, failures, mixed_dy, random_params
+from stagewise_common import (CONV_CASES, TORCH_F32, _ACT, conv_inputs, failures, mixed_dy,
+                              random_params)
 from test_gpu_parity import (_hub_batch, _shuffled_pairs, _sparse_batch, assert_g_close,
                              assert_y_close)
 
@@ -92,6 +96,8 @@ def _case_batches():
     cases = {
         "c01": (c1, 128, 3, "silu", True, {}, "b3"),
         "c02": (lambda: make_batch(6, 14, 16, n_mace=7, seed=102), 37, 2, "gelu", True, {}, "b3"),
+        "c02_h39": (lambda: make_batch(6, 14, 16, n_mace=7, seed=102), 39, 2, "gelu", True, {},
+                    "b3"),
         "c03": (lambda: make_batch(10, 24, 26, n_mace=2, seed=103), 96, 3, "relu", False, {},
                 "b3"),
         "c05": (lambda: make_batch(8, n_atoms=20, n_bonds=22, n_mace=16, seed=105), 528, 2, "silu",
@@ -104,6 +110,19 @@ def _case_batches():
         "c09_max": (lambda: _sparse_batch(6, 40, seed=29), 64, 2, "silu", False,
                     dict(pool="max"), "b3"),
         "c11": (c1, 128, 3, "silu", True, dict(p_drop=0.02), "b3"),
+        # H > 512: the fp32 TN kernels (both families are judged as fp32)
+        "c12": (lambda: make_batch(7, 21, 23, n_mace=40, seed=112), 1000, 2, "silu", True, {},
+                "f32"),
+        "c13": (lambda: make_batch(7, 21, 23, n_mace=7, seed=113), 515, 2, "gelu", True, {},
+                "f32"),
+        "c14": (lambda: make_batch(7, 21, 23, n_mace=2, seed=114), 521, 3, "relu", False, {},
+                "f32"),
+        "c15": (lambda: _hub_batch([150, 3, 70, 300, 5], seed=43), 520, 2, "relu", True, {},
+                "f32"),
+        "c16": (lambda: _sparse_batch(6, 40, seed=31), 516, 2, "silu", True,
+                dict(aggr="mean", pool="mean", p_drop=0.02), "f32"),
+        "c17": (lambda: _shuffled_pairs(make_batch(6, 21, 23, n_mace=2, seed=115), seed=5), 560,
+                2, "gelu", True, {}, "f32"),
     }
     for act in ACT_NAMES:
         cases["c10_" + act] = (c1, 128, 3, act, True, dict(scales=[1e-3, 1, 10, 100]), "b3")
@@ -258,3 +277,119 @@ def test_lost_low_pieces_pass_the_end_to_end_bars(small_case):
                        cache.get("skip_abs", {}).get(k) if k.startswith("skip") else None)
     assert_g_close(rec["dx"], gin["x"], "x")
     assert_g_close(rec["de"], gin["edge_attr"], "edge_attr")
+
+
+# ---------------------------------------------------------------------------------------------
+# the standalone DMPNNConv: oracle/stagewise.conv_stages (tests/test_gpu_conv_stagewise.py)
+# ---------------------------------------------------------------------------------------------
+def _conv_chain(i, ops=sw.REF, hooks=None):
+    return sw.conv_chain(i["edge_index"], i["N"], i["h"], i["weight"], i["bias"], i["grad_a"],
+                         i["grad_out"], i["mean"], ops, hooks)
+
+
+@pytest.mark.parametrize("case", ["h45_both", "h45_no_grad_a", "h45_no_grad_out",
+                                  "sparse_mean_h45"])
+def test_conv_stages_reproduce_torch_autograd(case):
+    """conv_stages fed its own float64 outputs: rho = 0, and equal to torch float64 autograd of
+    the reference conv (GNN.py: propagate, then lin(a[src] - flipped pairs of h))."""
+    i = conv_inputs(case)
+    rec = _conv_chain(i)
+    for name, got, st in sw.conv_stages(rec):
+        assert sw.rho(got, st)[0] == 0.0, name
+    ei = torch.from_numpy(i["edge_index"])
+    E, H, N = ei.shape[1], i["h"].shape[1], i["N"]
+    t8 = lambda a: torch.from_numpy(np.asarray(a, np.float64))  # noqa: E731
+    h, w, b = (t8(i[k]).clone().requires_grad_(True) for k in ("h", "weight", "bias"))
+    a = torch.zeros(N, H, dtype=torch.float64).index_add(0, ei[1], h)
+    if i["mean"]:  # PyG scatter mean: / max(count, 1)
+        a = a / torch.bincount(ei[1], minlength=N).clamp(min=1).double()[:, None]
+    rev = torch.flip(h.view(E // 2, 2, H), dims=[1]).reshape(E, H)
+    out = torch.nn.functional.linear(a[ei[0]] - rev, w, b)
+    loss = 0.0
+    if i["grad_a"] is not None:
+        loss = loss + (a * t8(i["grad_a"])).sum()
+    if i["grad_out"] is not None:
+        loss = loss + (out * t8(i["grad_out"])).sum()
+    loss.backward()
+
+    def close(got, ref, name):
+        ref = ref.detach().numpy()
+        err = np.abs(np.asarray(got) - ref).max() / (np.abs(ref).max() + 1e-300)
+        assert err <= 1e-12, (name, err)
+
+    close(rec["a"], a, "a")
+    close(rec["out"], out, "out")
+    close(rec["grad_h"], h.grad, "grad_h")
+    if i["grad_out"] is None:  # the ABI's zeroed gradients; autograd leaves them unset
+        assert w.grad is None and b.grad is None
+        assert not rec["grad_weight"].any() and not rec["grad_bias"].any()
+    else:
+        close(rec["grad_weight"], w.grad, "grad_weight")
+        close(rec["grad_bias"], b.grad, "grad_bias")
+
+
+@pytest.mark.parametrize("case", sorted(CONV_CASES))
+def test_conv_fp32_stand_in_meets_the_bars(case):
+    rows = sw.conv_judge(_conv_chain(conv_inputs(case), ops=sw.F32), TORCH_F32)
+    assert [r["stage"] for r in rows] == ["a", "out", "grad_weight", "grad_bias", "grad_h"]
+    assert all(np.isfinite(r["rho_ref"]) for r in rows)
+    bad = failures(rows)
+    assert not bad, "\n".join(bad)
+
+
+def _conv_mutations(i):
+    E = i["edge_index"].shape[1]
+
+    def paired_with_itself(out, rec):  # one edge's message formed from h[e] instead of h[e ^ 1]
+        e = 11
+        out = out.copy()
+        m = rec["a"][rec["edge_index"][0, e]] - rec["h"][e]
+        out[e] = (m.astype(np.float64) @ rec["weight"].T.astype(np.float64) + rec["bias"])
+        return out
+
+    def missing_last_split(dw, rec):  # the last split (2 rows of E = 322) left out of one tile
+        assert E % 64 == 2
+        m = sw.message(rec["a"], rec["h"], rec["edge_index"][0], np.arange(E) ^ 1)
+        dw = dw.copy()
+        dw[:16, :16] -= (np.asarray(rec["grad_out"][E - 2:, :16], np.float64).T
+                         @ m[E - 2:, :16]).astype(dw.dtype)
+        return dw
+
+    return {"out": paired_with_itself, "grad_weight": missing_last_split}
+
+
+@pytest.mark.parametrize("stage", ["out", "grad_weight"])
+def test_conv_one_element_bug_exceeds_its_stage_bar(stage):
+    i = conv_inputs("h45_both")
+    assert not failures(sw.conv_judge(_conv_chain(i, ops=sw.F32), TORCH_F32))
+    rec = _conv_chain(i, ops=sw.F32, hooks={stage: _conv_mutations(i)[stage]})
+    over = [r["stage"] for r in sw.conv_judge(rec, TORCH_F32) if not r["rho"] <= r["bar"]]
+    assert over == [stage], over
+
+
+def test_conv_in_degree_zero_scale_bug_exceeds_the_aggregate_bar():
+    """Mean aggregation's scale of a node without incoming edges, 1 / max(0, 1) = 1.  Its segment
+    sum is exactly 0 and in a paired edge list it is no edge's source either, so a scale of 0 in
+    place of 1 changes no output bit (asserted: nothing can observe it); the bug that scale
+    guards against, 1 / in-degree = inf, makes the row 0 * inf and exceeds the bar of ``a`` alone."""
+    i = conv_inputs("sparse_mean_h45")
+    deg = np.bincount(i["edge_index"][1], minlength=i["N"])
+    v = int(np.flatnonzero(deg == 0)[3])
+    assert v not in i["edge_index"]
+    clean = _conv_chain(i, ops=sw.F32)
+    assert not failures(sw.conv_judge(clean, TORCH_F32))
+
+    def scaled_by(s):
+        def hook(a, rec):
+            a = a.copy()
+            with np.errstate(invalid="ignore"):
+                a[v] = a[v] * np.float32(s)  # in place of the * 1 of inv_deg[v]
+            return a
+        return hook
+
+    zero = _conv_chain(i, ops=sw.F32, hooks={"a": scaled_by(0.0)})
+    for k in ("a", "out", "grad_weight", "grad_bias", "grad_h"):
+        assert zero[k].tobytes() == clean[k].tobytes(), k
+    rec = _conv_chain(i, ops=sw.F32, hooks={"a": scaled_by(np.inf)})
+    over = [r["stage"] for r in sw.conv_judge(rec, TORCH_F32) if not r["rho"] <= r["bar"]]
+    assert over == ["a"], over

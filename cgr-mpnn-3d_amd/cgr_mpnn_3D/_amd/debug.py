@@ -13,7 +13,10 @@ from .functional import _batch_struct, _dropout_array, _param_table, make_config
 
 class ArenaRun:
     def __init__(self, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, params,
-                 dropout_ps=None, seed=0, training=False, prepare_backward=True):
+                 dropout_ps=None, seed=0, training=False, prepare_backward=True,
+                 rng_counter=None):
+        """rng_counter: optional device int64 tensor [1], the dropout counter the forward reads
+        and advances when any layer drops (GNN._cgr_rng_counter's role); None: the key is seed."""
         lib = native.load()
         self.cfg = make_config(*cfg_tuple)
         self.N, self.E, self.B = int(x.shape[0]), int(edge_index.shape[1]), int(num_graphs)
@@ -23,7 +26,7 @@ class ArenaRun:
         nbytes = lib.cgr_gnn_arena_bytes(ctypes.byref(self.cfg), self.N, self.E, self.B)
         self.arena = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.y = torch.empty(self.B, dtype=torch.float32, device=dev)
-        self._keep = (x, edge_index, edge_attr, batch, graph_ptr, params)
+        self._keep = (x, edge_index, edge_attr, batch, graph_ptr, params, rng_counter)
         self.bs = _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, self.B)
         self.dropout_ps, self.seed, self.training = dropout_ps, seed, training
         # prepared for the backward (this helper runs it), as a training step's forward is
@@ -32,8 +35,8 @@ class ArenaRun:
         with native.device_guard(dev):
             native.check(lib.cgr_gnn_forward(
                 ctypes.byref(self.cfg), _param_table(params), ctypes.byref(self.bs),
-                _dropout_array(dropout_ps, self.cfg.depth), ctypes.c_uint64(seed), None,
-                self.flags, native.ptr(self.arena), native.ptr(self.y),
+                _dropout_array(dropout_ps, self.cfg.depth), ctypes.c_uint64(seed),
+                native.ptr(rng_counter), self.flags, native.ptr(self.arena), native.ptr(self.y),
                 native.stream_ptr(dev)))
 
     def offset(self, name, index=0):
@@ -45,6 +48,16 @@ class ArenaRun:
         off = self.offset(name)
         assert off >= 0, name
         return self.arena[off:off + 4 * count].view(torch.int32)
+
+    def uint64(self, name, count=1):
+        """count 64-bit words of a named buffer ("rng": the dropout key this forward used)."""
+        off = self.offset(name)
+        assert off >= 0 and off % 8 == 0, name
+        return self.arena[off:off + 8 * count].view(torch.int64)
+
+    def rng_key(self):
+        """The dropout key in the arena as a Python int in [0, 2^64) (synchronizes)."""
+        return int(self.uint64("rng").item()) % 2**64
 
     def floats(self, name, rows, index=0, cols=None):
         off = self.offset(name, index)

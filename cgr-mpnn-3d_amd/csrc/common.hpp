@@ -102,7 +102,9 @@ __device__ __forceinline__ float act_grad(float z, int act) {
 // element where a splitmix64 finaliser (64-bit multiplies) took ~30 -- the mask is evaluated for
 // all E*H elements in both the layer epilogue and layer_act_bwd.  Bijective in the low 32 index
 // bits for a fixed key; keep fractions and neighbour / cross-layer / cross-seed correlations
-// measured at the 1/sqrt(n) noise floor over 6.1M elements.
+// measured at the 1/sqrt(n) noise floor over 6.1M elements, and asserted on the host model of
+// this hash (oracle/dropout.py, tests/test_dropout_model.py: every |z| <= 4.5),
+// which tests/test_gpu_dropout_mask.py holds every evaluation site to, bit for bit.
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7feb352du;

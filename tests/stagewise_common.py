@@ -157,3 +157,65 @@ def conv_inputs(case):
                 weight=f4(rng.uniform(-k, k, (H, H))), bias=f4(rng.uniform(-k, k, H)),
                 grad_a=f4(rng.standard_normal((N, H))) if with_ga else None,
                 grad_out=f4(rng.standard_normal((E, H))) if with_go else None)
+
+
+# ---------------------------------------------------------------------------------------------
+# the dropout mask's cases, shared by tests/test_gpu_dropout_mask.py (every evaluation site of the
+# mask against oracle/dropout.py, bit for bit) and tests/test_dropout_model.py (what wrong masks
+# those shapes tell apart)
+# ---------------------------------------------------------------------------------------------
+MASK_D = 3  # conv layers 0, 1, 2 all occur
+
+# name: (batch, H, p, seed).  Seeds at or above 2^32 in m1, m3, m5 (the key's high half), 0 in m2.
+MASK_CASES = {
+    "m1": ("base", 64, 0.5, 2**40 + 1234567),  # fused forward, several 64-row tiles
+    "m2": ("base", 39, 0.25, 0),  # H % 4 == 3: the last float4 group partial, Hp = 40 != H
+    "m3": ("base", 516, 0.1, 0x9E3779B97F4A7C15 % 2**62),  # unfused forward (EpLayer), fp32 TNs
+    "m4": ("unpaired", 64, 0.5, 1234567),  # status 4: the unpaired completion form
+    "m5": ("hub", 64, 0.02, 2**62 - 1),  # hub segments spanning row tiles
+}
+
+
+def mask_batch(kind):
+    from test_gpu_parity import _hub_batch, _shuffled_pairs
+
+    from cgr_mpnn_3D._amd.synth import make_batch
+
+    if kind == "base":  # N 320, E 640: ten 64-row tiles
+        return make_batch(16, n_atoms=20, n_bonds=20, n_mace=0, seed=131)
+    if kind == "unpaired":  # edges shuffled inside every graph
+        return _shuffled_pairs(make_batch(16, n_atoms=20, n_bonds=20, n_mace=0, seed=132), seed=9)
+    if kind == "hub":  # E 1056: dst segments of 150 / 70 / 300 rows
+        return _hub_batch([150, 3, 70, 300, 5], seed=44)
+    raise KeyError(kind)
+
+
+def mask_model(case, ps=None):
+    """(batch, GNN on the CPU in train mode) of a mask case: sigmoid, so act(pre) > 0 and
+    h == 0 holds exactly where the element was dropped; learnable skip.  The hub case's layer
+    weights are scaled by 0.1: its in-degree-300 sums would otherwise push |pre| past 80, towards
+    where a float32 sigmoid underflows to 0."""
+    from cgr_mpnn_3D.models.GNN import GNN
+
+    kind, H, p, _ = MASK_CASES[case]
+    b = mask_batch(kind)
+    torch.manual_seed(17)
+    m = GNN(b.x.shape[1], b.edge_attr.shape[1], depth=MASK_D, hidden_sizes=[H] * MASK_D,
+            dropout_ps=[p] * MASK_D if ps is None else list(ps), activation_fn=torch.sigmoid,
+            use_learnable_skip=True)
+    with torch.no_grad():
+        for i, w in enumerate(m.skip_weights):
+            w.fill_(0.5 + 0.25 * i)
+        if kind == "hub":
+            for conv in m.convs:
+                conv.lin.weight.mul_(0.1)
+    return b, m.train()
+
+
+def model_masks(key, E, H, ps):
+    """oracle.dropout.keep_mask of every layer (None where the layer has no dropout): bool
+    [E, H] in dst-sorted edge order."""
+    from oracle import dropout as od
+
+    return [od.keep_mask(key, l, E, H, p) if od.thresh_scale(p)[0] else None
+            for l, p in enumerate(ps)]

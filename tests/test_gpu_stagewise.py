@@ -27,18 +27,21 @@ import pytest
 import torch
 
 from conftest import ACT_NAMES
-from stagewise_common import TORCH_F32, failures, mixed_dy, param_names, write_report
+from stagewise_common import (TORCH_F32, failures, mixed_dy, model_masks, param_names,
+                              write_report)
 from test_gpu_parity import ACT, _cfg_tuple, _hub_batch, _pool_fn, _shuffled_pairs, _sparse_batch
 
 from cgr_mpnn_3D._amd import native
 from cgr_mpnn_3D._amd.debug import ArenaRun
 from cgr_mpnn_3D._amd.synth import make_batch
 from cgr_mpnn_3D.models.GNN import GNN
+from oracle import dropout as od
 from oracle import stagewise as sw
 
 pytestmark = pytest.mark.gpu
 
 DY_SEED = 20261  # the one seed of every case's dy (stagewise_common.mixed_dy)
+DROP_SEED = 1234567  # the dropout seed of the cases that name none
 TN_CLASSES = {"readout": "gemm_tn_wgrad_readout", "layer": "gemm_tn_wgrad_layer",
               "node": "gemm_tn_wgrad_node"}
 
@@ -47,9 +50,9 @@ def _np(t):
     return t.detach().cpu().numpy().copy()
 
 
-def _run_once(cfg_t, data, B, params, dy, dropout_ps, training, inputs):
+def _run_once(cfg_t, data, B, params, dy, dropout_ps, training, inputs, drop_seed=DROP_SEED):
     run = ArenaRun(cfg_t, data.x, data.edge_index, data.edge_attr, data.batch, data.ptr, B, params,
-                   dropout_ps=dropout_ps, seed=1234567, training=training, prepare_backward=True)
+                   dropout_ps=dropout_ps, seed=drop_seed, training=training, prepare_backward=True)
     grads = run.backward(dy, params)
     gin = run.input_grads(dy, params, run.ws) if inputs else (None, None)
     torch.cuda.synchronize()
@@ -78,6 +81,7 @@ def _read(run, grads, gin, names, cfg, N, E, B):
     rec["grads"] = {k: _np(g) for k, g in zip(names, grads)}
     rec["dx"] = None if gin[0] is None else _np(gin[0])
     rec["de"] = None if gin[1] is None else _np(gin[1])
+    rec["key"] = run.rng_key() if run.training else None  # the dropout key the forward wrote
     return rec
 
 
@@ -93,7 +97,7 @@ def _flat(rec):
             yield from ((f"{k}.{n}", t) for n, t in v.items())
 
 
-def _tn_families(cfg_t, data, B, params, dy, dropout_ps, training):
+def _tn_families(cfg_t, data, B, params, dy, dropout_ps, training, drop_seed=DROP_SEED):
     """{"readout" | "layer" | "node": "b3" | "tnr" | "f32"} from the per-class profile of one run:
     the split-bf16 e-image TN (plain class name), the register-direct fp32 TN ("[tnr]") or the
     LDS-staged fp32 TN ("[f32]")."""
@@ -101,7 +105,7 @@ def _tn_families(cfg_t, data, B, params, dy, dropout_ps, training):
     lib.cgr_profile_reset()
     lib.cgr_profile_enable(1)
     try:
-        _run_once(cfg_t, data, B, params, dy, dropout_ps, training, False)
+        _run_once(cfg_t, data, B, params, dy, dropout_ps, training, False, drop_seed)
     finally:
         lib.cgr_profile_enable(0)
     classes = set(native.profile_report())
@@ -115,7 +119,10 @@ def _tn_families(cfg_t, data, B, params, dy, dropout_ps, training):
 
 
 def _stagewise(case, b, H, D, act, skip, dev, *, inputs=False, aggr="add", pool="add", p_drop=0.0,
-               x_row_scales=None, expect_tn=None, seed=0):
+               x_row_scales=None, expect_tn=None, seed=0, mask="recovered", drop_seed=DROP_SEED):
+    """mask: where the oracle's dropout masks come from.  "recovered": h != 0 of the GPU's own
+    output (checked against the host model's mask wherever the activation is not itself 0);
+    "model": oracle/dropout.py's keep_mask alone (sigmoid, so h == 0 exactly where dropped)."""
     F_, Fe = b.x.shape[1], b.edge_attr.shape[1]
     torch.manual_seed(seed)
     m = GNN(F_, Fe, depth=D, hidden_sizes=[H] * D, dropout_ps=[p_drop] * D,
@@ -142,12 +149,13 @@ def _stagewise(case, b, H, D, act, skip, dev, *, inputs=False, aggr="add", pool=
     training = p_drop > 0
     dps = [p_drop] * D if training else None
 
-    rec = _read(*_run_once(cfg_t, data, B, params, dy, dps, training, inputs), names, cfg, N, E, B)
-    rec2 = _read(*_run_once(cfg_t, data, B, params, dy, dps, training, inputs), names, cfg, N, E,
-                 B)
+    rec = _read(*_run_once(cfg_t, data, B, params, dy, dps, training, inputs, drop_seed), names,
+                cfg, N, E, B)
+    rec2 = _read(*_run_once(cfg_t, data, B, params, dy, dps, training, inputs, drop_seed), names,
+                 cfg, N, E, B)
     for (k, v), (_, v2) in zip(_flat(rec), _flat(rec2)):
         assert v.tobytes() == v2.tobytes(), f"{case}: {k} differs between two runs"
-    fam, classes = _tn_families(cfg_t, data, B, params, dy, dps, training)
+    fam, classes = _tn_families(cfg_t, data, B, params, dy, dps, training, drop_seed)
     if expect_tn is not None:
         assert fam == expect_tn, (fam, sorted(classes))
     # the oracle judges two arithmetics: split-bf16, and fp32 (both fp32 kernel families)
@@ -161,14 +169,34 @@ def _stagewise(case, b, H, D, act, skip, dev, *, inputs=False, aggr="add", pool=
     if pool == "mean":
         rec["inv_cnt"] = 1.0 / np.maximum(np.bincount(rec["node_graph"], minlength=B)[:B], 1)
     rec["keep"] = [None] * D
-    if training:  # the GPU's own dropout mask, as test_dropout_matches_oracle_with_recovered_mask
-        assert act != "relu"
+    model = [None] * D
+    if training:
+        assert act != "relu" and mask in ("recovered", "model")
+        assert rec["key"] == od.forward_key(drop_seed)  # no device counter: the key is the seed
+        model = model_masks(rec["key"], E, H, dps)
         for l in range(D):
-            kept = rec["h"][l + 1] != 0
-            live = np.abs(rec["pre"][l + 1]) > 1e-3
+            kept, pre = rec["h"][l + 1] != 0, rec["pre"][l + 1]
+            if mask == "model":  # the host model's mask, in the record's (dst-sorted) row order
+                assert act == "sigmoid" and np.isfinite(pre).all() and np.abs(pre).max() < 80
+                scale = float(od.thresh_scale(p_drop)[1])  # the kernels' float32; 0 at p >= 1
+                model[l] = model[l] & (scale > 0)
+                assert np.array_equal(kept, model[l]), _first_diff(case, l, kept, model[l])
+                rec["keep"][l] = model[l] * scale
+                continue
+            # the GPU's own dropout mask, as test_dropout_matches_oracle_with_recovered_mask
+            live = np.abs(pre) > 1e-3
             assert abs((1.0 - kept[live].mean()) - p_drop) < 0.01
             rec["keep"][l] = kept / (1.0 - p_drop)
+            # ... which is the model's wherever act(pre) is not itself 0 (pre 0, or far below 0)
+            assert not (kept & ~model[l]).any(), _first_diff(case, l, kept, model[l])
+            act_nonzero = (pre != 0) & (pre > -80)
+            assert np.array_equal(kept[act_nonzero], model[l][act_nonzero]), \
+                _first_diff(case, l, kept, model[l])
     rows = sw.judge(rec, sd, cfg, TORCH_F32)
+    for l in range(D):  # the backward regenerates the mask: dpre exactly 0 where the model drops
+        if model[l] is not None:
+            bad = (rec["dpre"][l] != 0) & ~model[l]
+            assert not bad.any(), f"{case}: dpre.{l} nonzero at dropped {np.argwhere(bad)[0]}"
     write_report(case, rows)
     for r in rows:
         print(f"{case:>14s} {r['stage']:<26s} rho {r['rho']:9.2f}  rho_ref {r['rho_ref']:7.2f}  "
@@ -176,6 +204,11 @@ def _stagewise(case, b, H, D, act, skip, dev, *, inputs=False, aggr="add", pool=
     bad = failures(rows)
     assert not bad, f"{case}:\n" + "\n".join(bad)
     return rec
+
+
+def _first_diff(case, l, kept, model):
+    d = np.argwhere(kept != model)
+    return f"{case}: layer {l} mask differs from the model at {len(d)} elements, first {d[:1]}"
 
 
 B3 = dict(readout="b3", layer="b3", node="b3")

@@ -295,42 +295,26 @@ WorkspaceLayout workspace_layout(const Dims& d) {
   W.img_side = b.take(b3_eimg_bytes(std::max(d.E, d.N), d.H));
   W.img_main = b.take(b3_eimg_bytes(d.N, d.H));
   W.img_top = b.take(b3_eimg_bytes(d.E, d.H));
-  // split-K slabs: every plan a call site may pick for its shape (gnn_bwd.hip), the largest wins.
-  // The side-stream weight gradients (readout, layers, edge features) run one after another and
-  // share `slab`; the node weight gradient runs beside them on the caller's stream: `slab2`.
-  size_t slab = 0, bslab = 0;
-  auto fit = [&](const TnPlan& p, int Nout, int Kout) {
-    slab = std::max(slab, (size_t)p.splits * Nout * (size_t)((Kout + 3) & ~3));  // rows to 4
-    bslab = std::max(bslab, (size_t)p.splits * Nout);
+  // split-K slabs: the largest over every family a site may pick for these dims (wgrad.hpp, the
+  // table gnn_bwd.hip launches through).  The side-stream weight gradients (readout, layers, edge
+  // features) run one after another and share `slab`; the node weight gradient runs beside them
+  // on the caller's stream: `slab2`.
+  auto fit = [&](WgSite s, size_t* slab, size_t* bslab) {
+    const WgCandidates w = wgrad_candidates(s, d);
+    for (int i = 0; i < w.n; ++i) {
+      *slab = std::max(*slab, w.c[i].slab_elems());
+      *bslab = std::max(*bslab, w.c[i].bslab_elems());
+    }
   };
-  auto tnr = [&](const TnrPlan& q) { return TnPlan{q.tiles_n, q.tiles_k, q.splits, q.rows_per_split}; };
-  const int Fx = d.F % 4 ? d.Fp : d.F;  // x columns the x-side GEMMs cover (pad columns zero)
-  const int Kr = Fx + d.H;              // readout: [x | s]
-  fit(tn_plan(d.H, Kr, (int)d.N), d.H, Kr);
-  fit(tnr(plan_tnr<5, 4>(d.H, Kr, (int)d.N, kTnrReadoutTarget)), d.H, Kr);
-  fit(b3tn_tnplan(d.H, Kr, (int)d.N, kB3TnReadoutTarget), d.H, Kr);
-  fit(tn_plan(d.H, d.H, (int)d.E), d.H, d.H);
-  fit(b3tn_tnplan(d.H, d.H, (int)d.E), d.H, d.H);
-  {
-    const int tf = tnr_layer_frags(d.H);
-    if (tf == 5) fit(tnr(plan_tnr<5, 5>(d.H, d.H, (int)d.E, kTnrLayerTarget)), d.H, d.H);
-    if (tf == 4) fit(tnr(plan_tnr<4, 4>(d.H, d.H, (int)d.E, kTnrLayerTarget)), d.H, d.H);
-  }
-  if (d.Fe > 0) fit(tn_plan(d.H, d.Fe, (int)d.E, kEdgeTnTargetWorkgroups), d.H, d.Fe);
-  W.slab_elems = slab;
-  W.bslab_elems = bslab;
-  W.slab = b.take(4 * std::max<size_t>(slab, 1));
-  W.bslab = b.take(4 * std::max<size_t>(bslab, 1));
-  W.slab_b = b.take(4 * std::max<size_t>(slab, 1));  // alternating with slab (gnn_bwd.hip)
-  W.bslab_b = b.take(4 * std::max<size_t>(bslab, 1));
-  slab = bslab = 0;
-  if (d.F > 0) {
-    fit(tn_plan(d.H, d.F, (int)d.N), d.H, d.F);
-    fit(tnr(plan_tnr<5, 4>(d.H, Fx, (int)d.N, kTnrNodeTarget)), d.H, Fx);
-    fit(b3tn_tnplan(d.H, Fx, (int)d.N, kB3TnNodeTarget), d.H, Fx);
-  }
-  W.slab2 = b.take(4 * std::max<size_t>(slab, 1));
-  W.bslab2 = b.take(4 * std::max<size_t>(bslab, 1));
+  for (WgSite s : {WgSite::Readout, WgSite::Layer, WgSite::Edge})
+    fit(s, &W.slab_elems, &W.bslab_elems);
+  fit(WgSite::Node, &W.slab2_elems, &W.bslab2_elems);
+  W.slab = b.take(4 * std::max<size_t>(W.slab_elems, 1));
+  W.bslab = b.take(4 * std::max<size_t>(W.bslab_elems, 1));
+  W.slab_b = b.take(4 * std::max<size_t>(W.slab_elems, 1));  // alternating with slab (gnn_bwd.hip)
+  W.bslab_b = b.take(4 * std::max<size_t>(W.bslab_elems, 1));
+  W.slab2 = b.take(4 * std::max<size_t>(W.slab2_elems, 1));
+  W.bslab2 = b.take(4 * std::max<size_t>(W.bslab2_elems, 1));
   W.dag = b.take(2 * 4 * N * Hp);  // two, alternating by layer
   // segment tickets, then one unpaired grid counter per fused layer-backward launch
   W.cnt = b.take(4 * (N * (size_t)layer_cols(d).tiles + CGR_MAX_DEPTH));

@@ -46,9 +46,9 @@ ConvLayout conv_layout(int64_t N, int64_t E, int64_t H) {
   L.dm = take(4 * E * Hp);
   L.da = take(4 * N * Hp);
   L.wT = take(4 * H * Hp);
-  const TnPlan p = tn_plan((int)H, (int)H, (int)E);
-  L.slab = take(4 * (size_t)p.splits * H * (size_t)((H + 3) & ~3));  // slab rows padded to 4
-  L.bslab = take(4 * (size_t)p.splits * H);
+  const WgChoice wg = wg_f32((int)H, (int)H, (int)E);  // dW = dout^T m (backward)
+  L.slab = take(4 * wg.slab_elems());
+  L.bslab = take(4 * wg.bslab_elems());
   L.inv_deg = take(4 * N);
   L.bytes = off;
   return L;
@@ -134,7 +134,7 @@ int cgr_dmpnn_conv_forward(const int64_t* edge_index, int64_t N, int64_t E, cons
       LdGatherDiff<true> al{a_p, h_p, src_c, nullptr, Hp};
       LdPlain<decltype(VW)::value> bl{weight, H};
       EpStore ep{h_out, H, (int)E, (int)H, bias};
-      return launch_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, (int)E, (int)H, (int)H, st);
+      return launch_gemm_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, (int)E, (int)H, (int)H, st);
     });
   });
   HIP_RET(e);
@@ -171,15 +171,12 @@ int cgr_dmpnn_conv_backward(const int64_t* edge_index, int64_t N, int64_t E, con
     {
       LdPlain<4> al{dout_p, Hp};
       LdGatherDiff<true> bl{a_p, h_p, src_c, nullptr, Hp};
-      const TnPlan p = tn_plan((int)H, (int)H, (int)E);
-      hipError_t e = with_tn_shape((int)H, (int)H, [&](auto W, auto RN) {
-        return launch_tn<decltype(W)::value, decltype(RN)::value>(
-            al, bl, p, P<float>(scratch, L.slab), P<float>(scratch, L.bslab), (int)H, (int)H,
-            (int)E, true, st);
-      });
-      HIP_RET(e);
-      HIP_RET(reduce_slabs(P<float>(scratch, L.slab), P<float>(scratch, L.bslab), p.splits,
-                           (int)H, (int)H, grad_weight, H, 0, grad_bias, st));
+      const WgChoice wg = wg_f32((int)H, (int)H, (int)E);  // as conv_layout sized the slabs
+      float* slab = P<float>(scratch, L.slab);
+      float* bslab = P<float>(scratch, L.bslab);
+      HIP_RET(wg_f32_launch(wg, al, bl, slab, bslab, true, st));
+      HIP_RET(reduce_slabs(slab, bslab, wg.plan.splits, wg.Nout, wg.Kout, grad_weight, H, 0,
+                           grad_bias, st));
     }
     TransposeJobs tj{};
     tj.job[0] = TransposeJob{weight, H, 0, wT, Hp, (int)H, (int)H};
@@ -189,7 +186,7 @@ int cgr_dmpnn_conv_backward(const int64_t* edge_index, int64_t N, int64_t E, con
       LdPlain<4> al{dout_p, Hp};
       LdPlain<4> bl{wT, Hp};
       EpStore ep{dm, Hp, (int)E, (int)H, nullptr};
-      return launch_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, (int)E, (int)H, (int)H, st);
+      return launch_gemm_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, (int)E, (int)H, (int)H, st);
     });
     HIP_RET(e);
     HIP_RET(segment_sum(dm, Hp, P<int>(scratch, L.src_perm), P<int>(scratch, L.src_ptr), N, Hp, da,

@@ -18,12 +18,14 @@
 //   dW0[:, F:] = dpre0^T e ; db0 = colsum(dpre0) ; dW0[:, :F] = (segsum_src dpre0)^T x
 //
 // Streams: the critical path is act_bwd -> the fused dm GEMM per layer.
-// Every weight-gradient TN GEMM (+ its slab reduction) only feeds the gradient outputs, so it runs on the side stream,
-// forked right after its input is produced; every layer's dpre has a buffer of its own (the
-// edge-init backward sums them into dh0), so the main stream waits for the side stream only at
-// the very end.
-#include <string>
-
+// Every weight-gradient TN GEMM (+ its slab reduction) only feeds the gradient outputs, so it runs
+// on the side stream, forked right after its input is produced; every layer's dpre has a buffer
+// of its own (the edge-init backward sums them into dh0), so the main stream waits for the side
+// stream only at the very end.
+//
+// Weight gradients: wgrad.hpp's wgrad_pick says which TN family runs a site and with which plan
+// (the table workspace_layout sized the slabs from); each site names its operands once per family
+// form and calls the `wgrad` helper below (slab check, launch, split-K reduction).
 #include "dispatch.hpp"
 #include "ep_bwd.hpp"
 #include "epilogues.hpp"
@@ -36,50 +38,26 @@ namespace cgr {
 
 void dropout_params(const float* dropout_p, int training, int l, uint32_t* thresh, float* scale);
 
-template <class AL, class BL>
-static hipError_t tn_gemm(const char* name, const AL& al, const BL& bl, int Nout, int Kout, int R,
-                          float* slab, float* bslab, bool want_bias, TnPlan* plan, hipStream_t st,
-                          int target = kTnTargetWorkgroups) {
-  *plan = tn_plan(Nout, Kout, R, target);
-  const TnPlan p = *plan;
-  // profile class "<name>[f32]": the fallback family is visible in the per-class report (tests
-  // assert which family ran for a width, bench.py keys its roofline on the plain names)
-  const std::string cls = std::string(name) + "[f32]";
-  ProfScope _p(cls.c_str(), st);
-  return with_tn_shape(Nout, Kout, [&](auto W, auto RN) {
-    return launch_tn<decltype(W)::value, decltype(RN)::value>(al, bl, p, slab, bslab,
-                                                                         Nout, Kout, R, want_bias,
-                                                                         st);
-  });
+// profile class of a weight gradient: the plain name for the split-bf16 e-image TN, "<name>[tnr]" /
+// "<name>[f32]" for the fp32 families, so the family is visible in the per-class report (tests
+// assert which family ran for a width, bench.py keys its roofline on the plain names)
+static const char* wgrad_class(WgSite s, WgFamily f) {
+#define CGR_WG_CLASS(name) {name, name "[tnr]", name "[f32]"}
+  static const char* const cls[4][3] = {
+      CGR_WG_CLASS("gemm_tn_wgrad_readout"), CGR_WG_CLASS("gemm_tn_wgrad_layer"),
+      CGR_WG_CLASS("gemm_tn_wgrad_node"), CGR_WG_CLASS("gemm_tn_wgrad_edge")};
+#undef CGR_WG_CLASS
+  return cls[(int)s][(int)f];
 }
 
-// register-direct strided-fragment TN (gemm_tnr.hpp); same slab layout as tn_gemm
-template <int FA, int FB, class SA, class SB>
-static hipError_t tnr_gemm(const char* name, const SA& sa, const SB& sb, int Nout, int Kout,
-                           int R, float* slab, float* bslab, bool want_bias, TnPlan* plan,
-                           hipStream_t st, int target = kTnrLayerTarget) {
-  const TnrPlan q = plan_tnr<FA, FB>(Nout, Kout, R, target);
-  *plan = TnPlan{q.tiles_n, q.tiles_k, q.splits, q.rows_per_split};
-  const std::string cls = std::string(name) + "[tnr]";  // "<name>[tnr]", as tn_gemm's "[f32]"
-  ProfScope _p(cls.c_str(), st);
-  return launch_gemm_tnr<FA, FB>(sa, sb, q, slab, bslab, Nout, Kout, R, want_bias, st);
-}
-
-// split-bf16 TN with the n-side operand A [R, Nout] as an e-image (gemm_b3.hpp): A was split
-// once into `img` (by its producer -- the dzn and top-layer dpre kernels, the Gs segmented sum --
-// or by b3_eimage), then every k-tile of the GEMM reads it pre-split
-// prev: a previous weight gradient's slab reduction folded into this launch (gemm_b3.hpp)
-template <class BL>
-static hipError_t b3tni_run(const char* name, const void* img, const BL& bl, int Nout, int Kout,
-                            int R, float* slab, float* bslab, bool want_bias, TnPlan* plan,
-                            hipStream_t st, int target = kB3TnTarget,
-                            const RedJob& prev = RedJob{}) {
-  const B3TnPlan q = b3tn_plan(Nout, Kout, R, target);
-  *plan = TnPlan{1, q.tiles_k, q.splits, q.rows_per_split};
-  ProfScope _p(name, st);
-  return launch_b3tni(B3EImg{static_cast<const b3_u4*>(img), b3_eimg_cols(Nout)}, bl, q, slab,
-                      bslab, Nout, Kout, R, want_bias, st, prev);
-}
+// where a weight gradient's reduced slabs go (reduce_slabs, kernels.hpp): w[n, col_off + k] and
+// bias[n] (nullptr: no bias sums wanted), the slab's pad columns [gap_at, gap_at + gap_len) skipped
+struct WgDst {
+  float* w;
+  int64_t ld, col_off;
+  float* bias;
+  int gap_at = 0, gap_len = 0;
+};
 
 // a split-K reduction waiting for its launch: folded into the next side-stream split-bf16 TN
 // (the launch-boundary reduce), or launched on its own (flush) before anything that would
@@ -88,23 +66,6 @@ struct PendingReduce {
   RedJob job{};  // job.slab == nullptr: none
   int bucket = -1;
 };
-static RedJob make_red_job(const TnPlan& p, const float* slab, const float* bslab, int Nout,
-                           int Kout, float* dst, int64_t ld_dst, int64_t col_off, float* bias_dst,
-                           int gap_at = 0, int gap_len = 0) {
-  RedJobs js{};
-  add_reduce_job(js, slab, bslab, p.splits, Nout, Kout, dst, ld_dst, col_off, bias_dst, gap_at,
-                 gap_len);
-  return js.n ? js.j[0] : RedJob{};
-}
-
-static hipError_t tn_reduce(const TnPlan& p, const float* slab, const float* bslab, int Nout,
-                            int Kout, float* dst, int64_t ld_dst, int64_t col_off, float* bias_dst,
-                            hipStream_t st, int gap_at = 0, int gap_len = 0, bool flat = false) {
-  ProfScope _p("splitk_reduce", st);
-  return reduce_slabs(slab, bslab, p.splits, Nout, Kout, dst, ld_dst, col_off, bias_dst, st,
-                      gap_at, gap_len, flat);
-}
-
 int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch* b,
                       const float* dropout_p, uint64_t seed, int training, const void* arena,
                       const float* dy, float* const* grads, void* workspace,
@@ -174,37 +135,64 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     }
     return retire();
   };
-  // the side TN writing slabs[sb] took pend's job as its prologue; its own becomes pending
-  auto fold = [&](const RedJob& mine, int bucket) -> int {
-    const int rc = retire();
-    if (rc) return rc;
-    pend.job = mine;
-    pend.bucket = bucket;
+  // One weight gradient: the picked family's TN (operands as wgrad_launch takes them, wgrad.hpp)
+  // into a slab pair checked to hold its plan, and its split-K reduction into o.  Side stream
+  // (readout, layer, edge) into slabs[sb]: a split-bf16 TN reduces pend's slabs in its prologue
+  // and leaves its own pending, an fp32 TN is followed by one launch for both; `bucket` is
+  // complete then.  Node: caller's stream, slab2, reduced at once (flat after a split-bf16 TN:
+  // this one ends the backward's main chain).
+  auto wgrad = [&](auto site, const WgChoice& c, const void* img, const float* a, int vec,
+                   auto&& make_b, const auto& tnr_b, const WgDst& o, int bucket,
+                   int max_blocks = kReduceMaxBlocks) -> int {
+    constexpr WgSite S = decltype(site)::value;
+    constexpr bool own = S == WgSite::Node;
+    const bool b3 = c.family == WgFamily::B3;
+    hipStream_t ws_st = own ? st : side;
+    float* sl = own ? slab2 : slabs[sb];
+    float* bsl = own ? bslab2 : bslabs[sb];
+    CGR_CHECK(c.slab_elems() <= (own ? WL.slab2_elems : WL.slab_elems) &&
+                  c.bslab_elems() <= (own ? WL.bslab2_elems : WL.bslab_elems),
+              "cgr: a weight-gradient plan exceeds the split-K slabs the workspace was sized for");
+    {
+      ProfScope _p(wgrad_class(S, c.family), ws_st);
+      HIP_RET((wgrad_launch<S>(c, img, a, Hp, vec, make_b, tnr_b, sl, bsl, o.bias != nullptr,
+                               ws_st, b3 && !own ? pend.job : RedJob{})));
+    }
+    if (own) {
+      ProfScope _p("splitk_reduce", st);
+      HIP_RET(reduce_slabs(sl, bsl, c.plan.splits, c.Nout, c.Kout, o.w, o.ld, o.col_off, o.bias, st,
+                           o.gap_at, o.gap_len, b3));
+      return 0;
+    }
+    RedJobs js{};  // (sized for the plan's split count)
+    add_reduce_job(js, sl, bsl, c.plan.splits, c.Nout, c.Kout, o.w, o.ld, o.col_off, o.bias,
+                   o.gap_at, o.gap_len);
+    const RedJob mine = js.n ? js.j[0] : RedJob{};
+    if (b3) {  // the TN took pend's job as its prologue; its own becomes pending
+      if (const int rc = retire()) return rc;
+      pend.job = mine;
+      pend.bucket = bucket;
+    } else {  // a TN that cannot fold: pend and its own reduction in one launch after it
+      if (const int rc = flush(&mine, max_blocks)) return rc;
+      if (bucket_events && bucket >= 0) HIP_RET(hipEventRecord(bucket_events[bucket], side));
+    }
     sb ^= 1;
     return 0;
   };
-  // a TN that cannot fold (fp32 families, the edge-feature TN): pend and its own reduction in one
-  // launch after it
-  auto unfolded = [&](const RedJob& mine, int bucket,
-                      int max_blocks = kReduceMaxBlocks) -> int {
-    const int rc = flush(&mine, max_blocks);
-    if (rc) return rc;
-    if (bucket_events && bucket >= 0) HIP_RET(hipEventRecord(bucket_events[bucket], side));
-    sb ^= 1;
-    return 0;
-  };
-
+  // x as the x-side weight gradients read it: in place, or the arena's padded copy (pad columns
+  // zero) when F % 4 != 0; Fx columns of it are covered
+  const float* xb = fv.xp ? fv.xp : b->x;
+  const int64_t ldx = fv.xp ? d.Fp : F;
+  const int Fx = (int)ldx;
+  const bool x_aligned = ((uintptr_t)b->x & 15) == 0;
 
   // side: dwf, dbf; dzn; dW_n = dzn^T [x | s], db_n (forked before the main stream's readout NT:
   // deferring it behind a layer, or enqueuing the NT first, A/B -4..-14 %).  dzn is materialised
   // for the weight gradient only: the main stream's NT forms it inside the GEMM (LdActGrad).
   // the split-bf16 e-image TN takes dzn as the e-image the dzn kernel writes (dzn itself is
   // then never stored); the fp32 families read dzn
-  const bool ro_b3 =
-      fv.xp ? (b3tni_ok(LdConcat<4>{fv.xp, d.Fp, fv.a[D], Hp, d.Fp}, H, N) &&
-               ((uintptr_t)fv.xp & 15) == 0)
-            : (F % 4 == 0 && ((uintptr_t)b->x & 15) == 0 &&
-               b3tni_ok(LdConcat<4>{b->x, F, fv.a[D], Hp, F}, H, N));
+  const WgChoice ro = wgrad_pick(WgSite::Readout, d, x_aligned);
+  const bool ro_b3 = ro.family == WgFamily::B3;
   const bool max_pool = fv.pool_arg != nullptr;  // global_max_pool (CGR_POOL_MAX)
   auto side_readout = [&]() -> int {
     {  // dwf = dy^T g, dbf: off the main chain (step A/B +0.8 %)
@@ -218,65 +206,15 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
                               Hp, d.act, ro_b3 ? nullptr : dzn, ro_b3 ? img_side : nullptr,
                               side, fv.inv_cnt));
     }
-    TnPlan p;
-    float* sl = slabs[sb];
-    float* bsl = bslabs[sb];
-    float* gW = grads[CGR_PARAM_E2N_W(D)];
-    float* gb = grads[CGR_PARAM_E2N_B(D)];
-    // bucket 0 (edge_to_node, ffn): complete once this reduction has run
-    if (fv.xp) {  // [xp | s] with x padded to Fp: the pad columns are skipped by the reduce
-      const int Fp = d.Fp;
-      LdPlain<4> al{dzn, Hp};
-      LdConcat<4> bl{fv.xp, Fp, fv.a[D], Hp, Fp};
-      const RedJob mine = make_red_job(TnPlan{}, sl, bsl, H, Fp + H, gW, F + H, 0, gb, F, Fp - F);
-      if (ro_b3) {
-        HIP_RET(b3tni_run("gemm_tn_wgrad_readout", img_side, bl, H, Fp + H, N, sl, bsl, true, &p,
-                          side, kB3TnReadoutTarget, pend.job));
-        RedJob j = mine;
-        red_job_set_splits(j, p.splits);
-        if (const int rc = fold(j, 0)) return rc;
-      } else {
-        if (tnr_x_ok(H, Fp + H, Fp, fv.xp)) {
-          HIP_RET((tnr_gemm<5, 4>("gemm_tn_wgrad_readout", TnrRows{dzn, Hp},
-                                  TnrConcat{fv.xp, Fp, fv.a[D], Hp, Fp}, H, Fp + H, N, sl, bsl,
-                                  true, &p, side, kTnrReadoutTarget)));
-        } else {
-          HIP_RET(tn_gemm("gemm_tn_wgrad_readout", al, bl, H, Fp + H, N, sl, bsl, true, &p,
-                          side));
-        }
-        RedJob j = mine;
-        red_job_set_splits(j, p.splits);
-        if (const int rc = unfolded(j, 0)) return rc;
-      }
-    } else {
-      const LdConcat<4> bl4{b->x, F, fv.a[D], Hp, F};
-      const RedJob mine = make_red_job(TnPlan{}, sl, bsl, H, F + H, gW, F + H, 0, gb);
-      if (ro_b3) {
-        HIP_RET(b3tni_run("gemm_tn_wgrad_readout", img_side, bl4, H, F + H, N, sl, bsl, true, &p,
-                          side, kB3TnReadoutTarget, pend.job));
-        RedJob j = mine;
-        red_job_set_splits(j, p.splits);
-        if (const int rc = fold(j, 0)) return rc;
-      } else {
-        if (F % 4 == 0 && tnr_x_ok(H, F + H, F, b->x)) {
-          HIP_RET((tnr_gemm<5, 4>("gemm_tn_wgrad_readout", TnrRows{dzn, Hp},
-                                  TnrConcat{b->x, F, fv.a[D], Hp, F}, H, F + H, N, sl, bsl, true,
-                                  &p, side, kTnrReadoutTarget)));
-        } else {
-          hipError_t e = with_vec(vec_for(b->x, F, F), [&](auto VX) {
-            LdPlain<4> al{dzn, Hp};
-            LdConcat<decltype(VX)::value> bl{b->x, F, fv.a[D], Hp, F};
-            return tn_gemm("gemm_tn_wgrad_readout", al, bl, H, F + H, N, sl, bsl, true, &p,
-                           side);
-          });
-          HIP_RET(e);
-        }
-        RedJob j = mine;
-        red_job_set_splits(j, p.splits);
-        if (const int rc = unfolded(j, 0)) return rc;
-      }
-    }
-    return 0;
+    // dW_n = dzn^T [x | s], db_n; bucket 0 (edge_to_node, ffn) is complete once its reduction
+    // has run.  With x padded to Fp the reduce skips the pad columns.
+    return wgrad(WgAt<WgSite::Readout>{}, ro, img_side, dzn, vec_for(xb, ldx, F),
+                 [&](auto V) {
+                   return LdConcat<decltype(V)::value>{xb, ldx, fv.a[D], Hp, Fx};
+                 },
+                 TnrConcat{xb, ldx, fv.a[D], Hp, Fx},
+                 WgDst{grads[CGR_PARAM_E2N_W(D)], F + H, 0, grads[CGR_PARAM_E2N_B(D)], F, Fx - F},
+                 0);
   };
   // main: ds = dzn W_n[:, F:] = diag(dy[graph]) act'(zn) (diag(wf) W_n[:, F:]) -- the row factor in
   // the epilogue, the column factor in the weight image (gnn_fwd.hip), act' in the A loader
@@ -356,8 +294,8 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   // launch 10 us, step 0.755 -> 0.769 ms, profiles/r05_rejected_epilogue_eimage_*.  Against
   // the top layer's pass on the side stream: same-box A/B 341.6k vs 341.1k reactions/s,
   // profiles/r05_ab2_top_eimage_fused_vs_side.txt.)
-  const bool top_b3 =
-      D > 0 && b3tni_ok(LdGatherDiff<false>{fv.a[D - 1], fv.h[D - 1], iv.src_s, iv.rev_s, Hp}, H, E);
+  const WgChoice ly = wgrad_pick(WgSite::Layer, d, true);  // (no x operand)
+  const bool top_b3 = D > 0 && ly.family == WgFamily::B3;
   if (D > 0) {  // top layer: dh_D = ds[dst]
     ProfScope _p("layer_act_bwd", st);
     LayerBwdArgs la = layer_args(D - 1);
@@ -422,43 +360,19 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     if (fork_ev) HIP_RET(hipStreamWaitEvent(side, fork_ev, 0));
     {  // side: dW_l = dpre^T m_l, db_l = colsum(dpre); the previous weight gradient's slabs are
        // reduced in the TN's prologue, this one's by the next TN (bucket D - l complete then)
-      LdPlain<4> al{dp, Hp};
-      LdGatherDiff<false> bl{fv.a[l], fv.h[l], iv.src_s, iv.rev_s, Hp};
-      TnPlan p;
-      float* sl = slabs[sb];
-      float* bsl = bslabs[sb];
-      RedJob mine = make_red_job(TnPlan{}, sl, bsl, H, H, grads[CGR_PARAM_CONV_W(l)], H, 0,
-                                 grads[CGR_PARAM_CONV_B(l)]);
-      const int tf = tnr_layer_frags(H);
-      if (l == D - 1 && top_b3) {
-        HIP_RET(b3tni_run("gemm_tn_wgrad_layer", img_top, bl, H, H, E, sl, bsl, true, &p, side,
-                          kB3TnTarget, pend.job));
-        red_job_set_splits(mine, p.splits);
-        if (const int rc = fold(mine, D - l)) return rc;
-      } else if (b3tni_ok(bl, H, E)) {
-        {
-          ProfScope _p("eimage", side);
-          HIP_RET(b3_eimage(dp, Hp, E, H, static_cast<b3_u4*>(img_side), side));
-        }
-        HIP_RET(b3tni_run("gemm_tn_wgrad_layer", img_side, bl, H, H, E, sl, bsl, true, &p, side,
-                          kB3TnTarget, pend.job));
-        red_job_set_splits(mine, p.splits);
-        if (const int rc = fold(mine, D - l)) return rc;
-      } else {
-        if (tf == 5) {
-          HIP_RET((tnr_gemm<5, 5>("gemm_tn_wgrad_layer", TnrRows{dp, Hp},
-                                  TnrDiff{fv.a[l], fv.h[l], iv.src_s, iv.rev_s, Hp}, H, H, E, sl,
-                                  bsl, true, &p, side)));
-        } else if (tf == 4) {
-          HIP_RET((tnr_gemm<4, 4>("gemm_tn_wgrad_layer", TnrRows{dp, Hp},
-                                  TnrDiff{fv.a[l], fv.h[l], iv.src_s, iv.rev_s, Hp}, H, H, E, sl,
-                                  bsl, true, &p, side)));
-        } else {
-          HIP_RET(tn_gemm("gemm_tn_wgrad_layer", al, bl, H, H, E, sl, bsl, true, &p, side));
-        }
-        red_job_set_splits(mine, p.splits);
-        if (const int rc = unfolded(mine, D - l)) return rc;
+      const void* img = l == D - 1 ? img_top : img_side;  // top layer: layer_act_bwd wrote it
+      if (ly.family == WgFamily::B3 && l < D - 1) {
+        ProfScope _p("eimage", side);
+        HIP_RET(b3_eimage(dp, Hp, E, H, static_cast<b3_u4*>(img_side), side));
       }
+      const int rc = wgrad(WgAt<WgSite::Layer>{}, ly, img, dp, 4,
+                           [&](auto) {
+                             return LdGatherDiff<false>{fv.a[l], fv.h[l], iv.src_s, iv.rev_s, Hp};
+                           },
+                           TnrDiff{fv.a[l], fv.h[l], iv.src_s, iv.rev_s, Hp},
+                           WgDst{grads[CGR_PARAM_CONV_W(l)], H, 0, grads[CGR_PARAM_CONV_B(l)]},
+                           D - l);
+      if (rc) return rc;
     }
   }
   float* gW0 = grads[CGR_PARAM_EDGE_INIT_W];
@@ -470,18 +384,12 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   auto edge_tn = [&]() -> int {
     if (Fe > 0) {  // dW0[:, F:] = dpre0^T e, db0
       if (tail_ev) HIP_RET(hipStreamWaitEvent(side, tail_ev, 0));
-      LdPlain<4> al{dpre0, Hp};
-      LdPlain<4> bl{fv.e_s, d.Fep};
-      TnPlan p;
-      float* sl = slabs[sb];
-      float* bsl = bslabs[sb];
-      HIP_RET(tn_gemm("gemm_tn_wgrad_edge", al, bl, H, Fe, E, sl, bsl, true, &p, side,
-                      kEdgeTnTargetWorkgroups));
-      // with the last layer's pending reduction, in one launch (bucket D + 1 is recorded at the
-      // join below)
-      // the last side-stream reduction: by the time it runs the main chain has ended (r05 trace:
-      // 13.5 us on 256 blocks for 1,300 logical ones, the step's tail), so it takes the GPU
-      return unfolded(make_red_job(p, sl, bsl, H, Fe, gW0, F + Fe, F, gb0), -1, 1 << 20);
+      // reduced with the last layer's pending reduction in one launch (bucket D + 1 is recorded
+      // at the join below), the last on the side stream: by then the main chain has ended (r05
+      // trace: 13.5 us on 256 blocks for 1,300 logical ones, the step's tail), so it takes the GPU
+      return wgrad(WgAt<WgSite::Edge>{}, wgrad_pick(WgSite::Edge, d, true), nullptr, dpre0, 4,
+                   [&](auto) { return LdPlain<4>{fv.e_s, d.Fep}; }, TnrRows{},
+                   WgDst{gW0, F + Fe, F, gb0}, -1, 1 << 20);
     }
     return flush();
   };
@@ -491,13 +399,8 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   }
   if (F > 0) {  // main: dW0[:, :F] = Gs^T x, Gs = segsum_src(dpre0) (own slab: beside the side
                 // stream's work)
-    const float* xb = fv.xp ? fv.xp : b->x;
-    const int64_t ldx = fv.xp ? d.Fp : F;
-    TnPlan p;
-    const int Fx = fv.xp ? d.Fp : F;  // x columns the GEMM covers (pad columns are zero)
-    const LdPlain<4> gbl{xb, ldx};
-    const bool b3 = ldx % 4 == 0 && ((uintptr_t)xb & 15) == 0 && b3tni_ok(gbl, H, N);
-    if (b3) {  // Gs straight into the TN's e-image (never stored in fp32)
+    const WgChoice nd = wgrad_pick(WgSite::Node, d, x_aligned);
+    if (nd.family == WgFamily::B3) {  // Gs straight into the TN's e-image (never stored in fp32)
       ProfScope _p("segsum_src_bwd", st);
       HIP_RET(b3_segsum_eimage(dpre0, Hp, iv.src_list, iv.src_ptr, N, H,
                                static_cast<b3_u4*>(img_main), st));
@@ -505,26 +408,12 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
       ProfScope _p("segsum_src_bwd", st);
       HIP_RET(segment_sum(dpre0, Hp, iv.src_list, iv.src_ptr, N, Hp, Gs, Hp, st));
     }
-    if (b3) {
-      HIP_RET(b3tni_run("gemm_tn_wgrad_node", img_main, gbl, H, Fx, N, slab2, bslab2, Fe == 0, &p,
-                        st, kB3TnNodeTarget));
-      // the flat reduce: this one ends the backward's main chain
-      HIP_RET(tn_reduce(p, slab2, bslab2, H, Fx, gW0, F + Fe, 0, Fe > 0 ? nullptr : gb0, st, F,
-                        Fx - F, true));
-    } else if (tnr_x_ok(H, Fx, ldx, xb)) {
-      HIP_RET((tnr_gemm<5, 4>("gemm_tn_wgrad_node", TnrRows{Gs, Hp}, TnrRows{xb, ldx}, H, Fx, N,
-                              slab2, bslab2, Fe == 0, &p, st, kTnrNodeTarget)));
-      HIP_RET(tn_reduce(p, slab2, bslab2, H, Fx, gW0, F + Fe, 0, Fe > 0 ? nullptr : gb0, st, F,
-                        Fx - F));
-    } else {
-      hipError_t e = with_vec(vec_for(xb, ldx, F), [&](auto VX) {
-        LdPlain<4> al{Gs, Hp};
-        LdPlain<decltype(VX)::value> bl{xb, ldx};
-        return tn_gemm("gemm_tn_wgrad_node", al, bl, H, F, N, slab2, bslab2, Fe == 0, &p, st);
-      });
-      HIP_RET(e);
-      HIP_RET(tn_reduce(p, slab2, bslab2, H, F, gW0, F + Fe, 0, Fe > 0 ? nullptr : gb0, st));
-    }
+    // db0 comes from the edge-feature TN when there is one
+    const int rc = wgrad(WgAt<WgSite::Node>{}, nd, img_main, Gs, vec_for(xb, ldx, F),
+                         [&](auto V) { return LdPlain<decltype(V)::value>{xb, ldx}; },
+                         TnrRows{xb, ldx},
+                         WgDst{gW0, F + Fe, 0, Fe > 0 ? nullptr : gb0, F, nd.Kout - F}, -1);
+    if (rc) return rc;
   } else if (Fe == 0) {
     HIP_RET(hipMemsetAsync(gb0, 0, sizeof(float) * H, st));
   }
@@ -574,7 +463,7 @@ int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* 
     const LdPlain<4> bl{fv.w0eT, Hp};
     const EpStorePermRows ep{de, Fe, E, Fe, iv.perm};
     HIP_RET(with_nt_rn(Fe, [&](auto RN) {
-      return launch_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, E, Fe, H, st);
+      return launch_gemm_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, E, Fe, H, st);
     }));
   }
   if (dx && F > 0) {
@@ -600,7 +489,7 @@ int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* 
     HIP_RET(with_vec(H % 4 == 0 ? 4 : (H % 2 == 0 ? 2 : 1), [&](auto V) {
       const LdConcat<decltype(V)::value> al{Gs, Hp, dzn, Hp, H};
       return with_nt_rn(F, [&](auto RN) {
-        return launch_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, N, F, 2 * H, st);
+        return launch_gemm_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, N, F, 2 * H, st);
       });
     }));
   }

@@ -119,9 +119,11 @@ struct ArenaLayout {
 // layer-backward GEMM hands to the completer of a tile-crossing segment (ep_bwd.hpp).
 struct WorkspaceLayout {
   size_t bytes;
-  size_t dpre, dm, dh0, dzn, ds, Gs, slab, bslab, slab2, bslab2, dsig_part, slab_elems,
-      bslab_elems;
+  size_t dpre, dm, dh0, dzn, ds, Gs, slab, bslab, slab2, bslab2, dsig_part;
   size_t slab_b, bslab_b;  // the side stream's second slab pair (reductions folded into TNs)
+  // floats each slab / bias slab holds (slab, slab_b; slab2): the backward checks the plan it
+  // picked against them before every weight-gradient launch
+  size_t slab_elems = 0, bslab_elems = 0, slab2_elems = 0, bslab2_elems = 0;
   // split-bf16 e-images (gemm_b3.hpp B3EImg) of the weight gradients' shared operand: dpre_l and
   // dzn on the side stream (one at a time), Gs on the caller's stream; the top layer's dpre,
   // written by its activation kernel on the caller's stream (img_top)

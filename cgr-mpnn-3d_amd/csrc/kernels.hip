@@ -624,6 +624,19 @@ __global__ __launch_bounds__(kRedCols * kRedGroups) void k_reduce_slabs(RedJobs 
   }
 }
 
+// size a job's logical blocks for its split count (reduce_slab_block's two forms)
+static void red_job_set_splits(RedJob& J, int splits) {
+  J.splits = splits;
+  const int64_t nf = (int64_t)J.Nout * (((J.Kout + 3) & ~3) >> 2);
+  if (splits < kRedGroups) {  // flat logical blocks (reduce_slab_block)
+    J.main_blocks = (int)cdiv(nf + (J.bias_dst ? J.Nout : 0), kRedCols * kRedGroups);
+    J.nblk = J.main_blocks;
+  } else {
+    J.main_blocks = (int)cdiv(nf, kRedCols);
+    J.nblk = J.main_blocks + (J.bias_dst ? (int)cdiv(J.Nout, kRedCols) : 0);
+  }
+}
+
 bool add_reduce_job(RedJobs& jobs, const float* slab, const float* bslab, int splits, int Nout,
                     int Kout, float* dst, int64_t ld_dst, int64_t col_off, float* bias_dst,
                     int gap_at, int gap_len) {
@@ -646,18 +659,6 @@ bool add_reduce_job(RedJobs& jobs, const float* slab, const float* bslab, int sp
   red_job_set_splits(J, splits);
   jobs.total += J.nblk;
   return true;
-}
-
-void red_job_set_splits(RedJob& J, int splits) {
-  J.splits = splits;
-  const int64_t nf = (int64_t)J.Nout * (((J.Kout + 3) & ~3) >> 2);
-  if (splits < kRedGroups) {  // flat logical blocks (reduce_slab_block)
-    J.main_blocks = (int)cdiv(nf + (J.bias_dst ? J.Nout : 0), kRedCols * kRedGroups);
-    J.nblk = J.main_blocks;
-  } else {
-    J.main_blocks = (int)cdiv(nf, kRedCols);
-    J.nblk = J.main_blocks + (J.bias_dst ? (int)cdiv(J.Nout, kRedCols) : 0);
-  }
 }
 
 hipError_t reduce_slabs_batched(const RedJobs& jobs, int max_blocks, hipStream_t st) {

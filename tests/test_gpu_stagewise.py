@@ -53,6 +53,7 @@ def _np(t):
 def _run_once(cfg_t, data, B, params, dy, dropout_ps, training, inputs, drop_seed=DROP_SEED):
     run = ArenaRun(cfg_t, data.x, data.edge_index, data.edge_attr, data.batch, data.ptr, B, params,
                    dropout_ps=dropout_ps, seed=drop_seed, training=training, prepare_backward=True)
+    assert run.bs.x == data.x.data_ptr()  # the x pointer the library is handed
     grads = run.backward(dy, params)
     gin = run.input_grads(dy, params, run.ws) if inputs else (None, None)
     torch.cuda.synchronize()
@@ -119,8 +120,11 @@ def _tn_families(cfg_t, data, B, params, dy, dropout_ps, training, drop_seed=DRO
 
 
 def _stagewise(case, b, H, D, act, skip, dev, *, inputs=False, aggr="add", pool="add", p_drop=0.0,
-               x_row_scales=None, expect_tn=None, seed=0, mask="recovered", drop_seed=DROP_SEED):
-    """mask: where the oracle's dropout masks come from.  "recovered": h != 0 of the GPU's own
+               x_row_scales=None, expect_tn=None, seed=0, mask="recovered", drop_seed=DROP_SEED,
+               x_offset=0):
+    """x_offset: x handed to the library as a contiguous view that many floats into a larger
+    device buffer (pointer % 16 == 4 * x_offset).
+    mask: where the oracle's dropout masks come from.  "recovered": h != 0 of the GPU's own
     output (checked against the host model's mask wherever the activation is not itself 0);
     "model": oracle/dropout.py's keep_mask alone (sigmoid, so h == 0 exactly where dropped)."""
     F_, Fe = b.x.shape[1], b.edge_attr.shape[1]
@@ -142,6 +146,11 @@ def _stagewise(case, b, H, D, act, skip, dev, *, inputs=False, aggr="add", pool=
                                                       None]).astype(np.float32)
     data = b.to_torch(dev)
     data.x = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    if x_offset:
+        buf = torch.zeros(x.size + 4, dtype=torch.float32, device=dev)
+        view = buf[x_offset:x_offset + x.size].view(x.shape)
+        data.x = view.copy_(data.x)
+        assert data.x.is_contiguous() and data.x.data_ptr() % 16 == 4 * x_offset
     N, E, B = x.shape[0], b.edge_index.shape[1], b.num_graphs
     cfg_t = _cfg_tuple(F_, Fe, H, D, act, skip, aggr, pool)
     cfg = dict(F=F_, Fe=Fe, H=H, D=D, act=act, skip=skip, aggr=aggr, pool=pool, batched=True)
@@ -317,10 +326,11 @@ def test_case11_train_mode_dropout(cuda_device):
 
 # ---------------------------------------------------------------------------------------------
 # H > 512: edge_init_fwd + segment_sum, a plain EpLayer launch + segment_sum per layer, every
-# weight gradient on one of the fp32 TN kernels, chosen in gnn_bwd.hip from divisibility:
-#   layer    tnr<5, 5> (H % 5 == 0), else tnr<4, 4> (H % 4 == 0), else the LDS-staged tn_gemm
-#   readout  tnr<5, 4> over [x | a_D] when H % 5 == 0 and (Fp + H) % 4 == 0, else tn_gemm
-#   node     tnr<5, 4> when H % 5 == 0 (x columns padded to Fp, or F % 4 == 0), else tn_gemm
+# weight gradient on one of the fp32 TN kernels, chosen in csrc/wgrad.hpp from divisibility:
+#   layer    tnr<5, 5> (H % 5 == 0), else tnr<4, 4> (H % 4 == 0), else the LDS-staged fp32 TN
+#   readout  tnr<5, 4> over [x | a_D] when H % 5 == 0 and (Fp + H) % 4 == 0, else LDS-staged
+#   node     tnr<5, 4> when H % 5 == 0 (x columns padded to Fp, or F % 4 == 0), else LDS-staged
+# (the tnr x-side forms also need x itself 16-byte aligned when it is read in place)
 # The batches have E = 2 (mod 4) and an odd N unless said otherwise: the tnr waves' last 4-row
 # step and the last split-K split are partial.
 # ---------------------------------------------------------------------------------------------
@@ -338,7 +348,7 @@ def test_case12_sweep_width(cuda_device):
 
 def test_case13_mixed_families_padded_width(cuda_device):
     # H = 515 (Hp = 516), F = 85 -> Fp = 88: H % 5 == 0 but (Fp + H) % 4 != 0, so the readout
-    # runs tn_gemm and the other two tnr within one backward; the layer TN's 6 splits of 64 rows
+    # runs the LDS-staged TN and the other two tnr within one backward; the layer TN's 6 splits of 64 rows
     # over E = 322 leave 2 rows to the last
     b = _wide_batch(7, 113)
     assert (b.edge_index.shape[1], b.x.shape[1]) == (322, 85)
@@ -347,7 +357,7 @@ def test_case13_mixed_families_padded_width(cuda_device):
 
 
 def test_case14_prime_width_relu_x_in_place(cuda_device):
-    # H = 521 (prime): every weight gradient on tn_gemm; F = 80: x read in place; ReLU
+    # H = 521 (prime): every weight gradient on the LDS-staged TN; F = 80: x read in place; ReLU
     b = _wide_batch(2, 114)
     assert b.x.shape[1] == 80
     _stagewise("c14_relu_h521", b, 521, 3, "relu", False, cuda_device, inputs=True, expect_tn=F32)
@@ -378,6 +388,16 @@ def test_case17_unpaired_order_unpadded_x_tnr(cuda_device):
     torch.cuda.synchronize()
     bits = native.raise_device_errors(cuda_device)  # raises on a completion timeout
     assert bits & native.DEVERR_UNPAIRED_SEEN
+
+
+def test_case17_x_two_floats_off_16_bytes(cuda_device):
+    # case 17's batch (edges in paired order) with x starting two floats into its buffer (pointer
+    # % 16 == 8): the two-wide loaders (x-GEMM, LdConcat<2> / LdPlain<2> of the LDS-staged fp32
+    # TN); H = 560 would put the x-side gradients on tnr<5, 4>, refused on the alignment alone
+    b = _wide_batch(2, 115, graphs=6)
+    assert b.x.shape[1] == 80
+    _stagewise("c17_gelu_h560_x8", b, 560, 2, "gelu", True, cuda_device, x_offset=2,
+               expect_tn=dict(layer="tnr", readout="f32", node="f32"))
 
 
 def test_predict_rings_equal_training_forward_bitwise_h1000(cuda_device):

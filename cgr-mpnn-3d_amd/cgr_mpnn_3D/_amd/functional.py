@@ -18,10 +18,26 @@ from . import native
 
 
 def make_config(num_node_features, num_edge_features, hidden, depth, act_code, learnable_skip,
-                aggregation=0, pooling=0):
+                aggregation=0, pooling=0, precision=None):
+    """precision: enum cgr_precision (0 split-bf16, 1 fp32); None takes the process switch
+    (config.precision) as it stands when this is called."""
+    if precision is None:
+        precision = _config.precision_code()
     return native.CgrGnnConfig(int(num_node_features), int(num_edge_features), int(hidden),
                                int(depth), int(act_code), 1 if learnable_skip else 0,
-                               int(aggregation), int(pooling))
+                               int(aggregation), int(pooling), int(precision))
+
+
+def resolve_config_tuple(cfg_tuple):
+    """The config tuple with its precision mode spelled out as the ninth element (a shorter tuple
+    follows the process switch, read here, once): the tuple that builds the config is then also
+    the key of every size memo and what the autograd context keeps for the backward."""
+    t = tuple(cfg_tuple)
+    if len(t) < 8:
+        t = t + (0,) * (8 - len(t))  # aggregation, pooling defaults
+    if len(t) == 8 or t[8] is None:
+        t = t[:8] + (_config.precision_code(),)
+    return t
 
 
 def _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, num_graphs):
@@ -133,6 +149,7 @@ class GNNFunction(torch.autograd.Function):
     def forward(ctx, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
                 dropout_ps, seed, rng_counter, training, bucket_hook, *params):
         lib = native.load()
+        cfg_tuple = resolve_config_tuple(cfg_tuple)  # the mode of this forward AND its backward
         cfg = make_config(*cfg_tuple)
         N, E, B = int(x.shape[0]), int(edge_index.shape[1]), int(num_graphs)
         dev = x.device
@@ -230,6 +247,7 @@ def gnn_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graph
     a replayed captured step) updates the parameters through raw pointers, and no buffer shared
     with a predict still running on another stream."""
     lib = native.load()
+    cfg_tuple = resolve_config_tuple(cfg_tuple)
     cfg = make_config(*cfg_tuple)
     N, E, B = int(x.shape[0]), int(edge_index.shape[1]), int(num_graphs)
     dev = x.device

@@ -15,11 +15,12 @@ _LIB_NAME = "libcgr_mpnn3d.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CGR_MPNN3D_LIB", os.path.join(_HERE, "lib", _LIB_NAME))
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 TRAIN_DROPOUT, TRAIN_FOR_BACKWARD = 1, 2  # cgr_gnn_forward / _backward `training` bits
 MAX_DEPTH = 32
 ACT_RELU, ACT_SILU, ACT_GELU = 0, 1, 2
 ACT_TANH, ACT_SIGMOID, ACT_ELU, ACT_LEAKY_RELU, ACT_SOFTPLUS, ACT_MISH, ACT_SELU = 3, 4, 5, 6, 7, 8, 9
+PRECISION_SPLIT, PRECISION_FP32 = 0, 1  # enum cgr_precision
 ACT_NAMES = ("relu", "silu", "gelu", "tanh", "sigmoid", "elu", "leaky_relu", "softplus", "mish",
              "selu")  # index = cgr_activation code (include/cgr_mpnn3d.h)
 
@@ -34,6 +35,7 @@ class CgrGnnConfig(ctypes.Structure):
         ("learnable_skip", c_int32),
         ("aggregation", c_int32),
         ("pooling", c_int32),
+        ("precision", c_int32),  # enum cgr_precision (ABI 9): 0 split-bf16 (default), 1 fp32
     ]
 
 

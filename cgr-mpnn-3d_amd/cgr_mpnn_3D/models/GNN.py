@@ -279,7 +279,10 @@ class GNN(nn.Module):
         counter = self._cgr_rng_counter
         if counter.device != dev:
             counter = self._cgr_rng_counter = counter.to(dev)
-        cfg = (F_, Fe, H, self.depth, act, self.use_learnable_skip, aggr, pool)
+        # ninth element: the precision mode (config.precision) resolved here, once per forward --
+        # the backward runs in the mode its forward ran in, whatever the switch says by then
+        cfg = (F_, Fe, H, self.depth, act, self.use_learnable_skip, aggr, pool,
+               _config.precision_code())
         if not (torch.is_grad_enabled() and want_grad):
             # no gradient wanted (test.py / the CLI run under torch.no_grad()): the forward-only
             # path, no saved activations

@@ -23,16 +23,26 @@ void set_error(const std::string& msg) { g_err = msg; }
 // them, so the table stays as small as the set of live arena blocks.
 static std::mutex g_arena_mu;
 static std::unordered_map<const void*, int> g_arena_flags;
+// ... and the precision mode it ran in (enum cgr_precision): the arena's images, counters and
+// saved activations are laid out and filled for that mode, so the backward and the input
+// gradients must be given a config of the same mode
+static std::unordered_map<const void*, int> g_arena_mode;
 // every forward into an arena starts a new generation of it; a backward enqueued on (arena,
 // generation) records its workspace, and cgr_gnn_input_grads -- which reads dpre0 and the
 // readout's operands from that workspace -- requires the record to name the same arena at its
 // current generation (otherwise it silently returned garbage)
 static std::unordered_map<const void*, uint64_t> g_arena_gen;
 static std::unordered_map<const void*, std::pair<const void*, uint64_t>> g_ws_backward;
-static void note_forward(const void* arena, int flags) {
+static void note_forward(const void* arena, int flags, int mode = -1) {
   std::lock_guard<std::mutex> lk(g_arena_mu);
   g_arena_flags[arena] = flags;
+  g_arena_mode[arena] = mode;
   ++g_arena_gen[arena];
+}
+static int forward_mode(const void* arena) {
+  std::lock_guard<std::mutex> lk(g_arena_mu);
+  const auto it = g_arena_mode.find(arena);
+  return it == g_arena_mode.end() ? -1 : it->second;
 }
 static int forward_flags(const void* arena) {
   std::lock_guard<std::mutex> lk(g_arena_mu);
@@ -79,6 +89,7 @@ Dims make_dims(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B) {
   d.learnable_skip = cfg->learnable_skip ? 1 : 0;
   d.aggr = cfg->aggregation;
   d.pool = cfg->pooling;
+  d.precision = cfg->precision;
   return d;
 }
 
@@ -110,8 +121,9 @@ static void layout_prefix(const Dims& d, ArenaLayout& L, Bump& b) {
   // + the ticket counters of the layer GEMMs' hub segments (EpLayerSeg: zero on entry, reset by
   // each completer)
   L.fcnt = L.status + 16;
-  // the layer forward runs in layer_cols(d), or in b3_cols(H) over caller-packed images (predict)
-  const B3Cols lc = layer_cols(d), dc = b3_cols(d.H);
+  // the layer forward runs in layer_cols(d), or in image_cols(d, H) over caller-packed images
+  // (predict)
+  const B3Cols lc = layer_cols(d), dc = image_cols(d, d.H);
   const size_t fcnt_n = N * (size_t)std::max(lc.tiles, dc.tiles);
   L.zero_bytes = (size_t)round_up((int64_t)(4 * (4 * N + B) + 16 + 4 * fcnt_n), 16);
   b.take(L.zero_bytes);
@@ -148,9 +160,9 @@ ArenaLayout arena_layout(const Dims& d) {
   Bump b;
   const size_t N = (size_t)d.N, E = (size_t)d.E, B = (size_t)d.B, Hp = (size_t)d.Hp;
   layout_prefix(d, L, b);
-  L.b3x = d.F > 0 ? b.take(16 * b3_img_u4(b3nt_cols((int)d.N, 2 * d.H), d.F)) : kNone;
-  // the node-row readout GEMMs in their grid-filling column tiling (b3nt_cols)
-  const B3Cols rc = b3nt_cols((int)d.N, d.H);
+  L.b3x = d.F > 0 ? b.take(16 * b3_img_u4(x_cols(d), d.F)) : kNone;
+  // the node-row readout GEMMs in their grid-filling column tiling (readout_cols)
+  const B3Cols rc = readout_cols(d);
   L.b3rof = b.take(16 * b3_img_u4(rc, d.H));
   L.b3rob = b.take(16 * b3_img_u4(rc, d.H));
   for (int l = 0; l < d.D; ++l) {
@@ -187,8 +199,8 @@ ArenaLayout eval_arena_layout(const Dims& d) {
   L.hn = b.take(4 * N * Hp);
   L.g = b.take(4 * B * Hp);
   // forward weight images, packed by every predict that is not handed pre-packed ones
-  L.b3x = d.F > 0 ? b.take(16 * b3_img_u4(b3nt_cols((int)d.N, 2 * d.H), d.F)) : kNone;
-  L.b3rof = b.take(16 * b3_img_u4(b3nt_cols((int)d.N, d.H), d.H));
+  L.b3x = d.F > 0 ? b.take(16 * b3_img_u4(x_cols(d), d.F)) : kNone;
+  L.b3rof = b.take(16 * b3_img_u4(readout_cols(d), d.H));
   for (int l = 0; l < d.D; ++l) L.b3lf[l] = b.take(16 * b3_img_u4(layer_cols(d), d.H));
   L.bytes = b.off;
   L.off_index_begin = 0;
@@ -198,9 +210,10 @@ ArenaLayout eval_arena_layout(const Dims& d) {
 ImageLayout image_layout(const Dims& d) {
   ImageLayout I;
   Bump b;
-  I.b3x = d.F > 0 ? b.take(16 * b3_img_u4(2 * d.H, d.F)) : kNone;
-  I.b3rof = b.take(16 * b3_img_u4(d.H, d.H));
-  for (int l = 0; l < CGR_MAX_DEPTH; ++l) I.b3lf[l] = l < d.D ? b.take(16 * b3_img_u4(d.H, d.H)) : kNone;
+  const B3Cols cx = image_cols(d, 2 * d.H), ch = image_cols(d, d.H);
+  I.b3x = d.F > 0 ? b.take(16 * b3_img_u4(cx, d.F)) : kNone;
+  I.b3rof = b.take(16 * b3_img_u4(ch, d.H));
+  for (int l = 0; l < CGR_MAX_DEPTH; ++l) I.b3lf[l] = l < d.D ? b.take(16 * b3_img_u4(ch, d.H)) : kNone;
   I.bytes = b.off;
   return I;
 }
@@ -268,7 +281,14 @@ FloatView float_view(void* arena, const ArenaLayout& L, const Dims& d) {
 // column tiling of the layer GEMMs (forward and fused backward) over this batch's E rows: b3_cols
 // when that fills the chip, else the narrower tiles of b3nt_cols (small batches: train.py's 32
 // reactions run 60 -> 210 workgroups per layer GEMM)
-B3Cols layer_cols(const Dims& d) { return b3nt_cols((int)d.E, d.H); }
+// (every tiling in d's precision mode: the per-k-step accumulation variant of the NT kernel runs
+// narrower tiles, gemm_b3.hpp kB3AccMaxNf)
+B3Cols layer_cols(const Dims& d) { return b3nt_cols((int)d.E, d.H, d.nt_acc()); }
+// the x-GEMM's and the readout GEMMs' grid-filling tilings over this batch's N rows
+B3Cols x_cols(const Dims& d) { return b3nt_cols((int)d.N, 2 * d.H, d.nt_acc()); }
+B3Cols readout_cols(const Dims& d) { return b3nt_cols((int)d.N, d.H, d.nt_acc()); }
+// caller-packed images (cgr_gnn_pack_images) know no batch: b3_cols
+B3Cols image_cols(const Dims& d, int n) { return b3_cols(n, d.nt_acc()); }
 
 // row tiles x column tiles of the fused layer-backward GEMM (gnn_bwd.hip, ep_bwd.hpp)
 int bwd_seg_tiles(const Dims& d) {
@@ -292,9 +312,15 @@ WorkspaceLayout workspace_layout(const Dims& d) {
   W.dzn = b.take(4 * N * Hp);
   W.ds = b.take(4 * N * Hp);
   W.Gs = b.take(4 * N * Hp);
-  W.img_side = b.take(b3_eimg_bytes(std::max(d.E, d.N), d.H));
-  W.img_main = b.take(b3_eimg_bytes(d.N, d.H));
-  W.img_top = b.take(b3_eimg_bytes(d.E, d.H));
+  // e-images: only where a site lists the split-bf16 family (not in CGR_PRECISION_FP32)
+  bool eimg = false;
+  for (WgSite s : {WgSite::Readout, WgSite::Layer, WgSite::Node}) {
+    const WgCandidates w = wgrad_candidates(s, d);
+    for (int i = 0; i < w.n; ++i) eimg = eimg || w.c[i].family == WgFamily::B3;
+  }
+  W.img_side = b.take(eimg ? b3_eimg_bytes(std::max(d.E, d.N), d.H) : 0);
+  W.img_main = b.take(eimg ? b3_eimg_bytes(d.N, d.H) : 0);
+  W.img_top = b.take(eimg ? b3_eimg_bytes(d.E, d.H) : 0);
   // split-K slabs: the largest over every family a site may pick for these dims (wgrad.hpp, the
   // table gnn_bwd.hip launches through).  The side-stream weight gradients (readout, layers, edge
   // features) run one after another and share `slab`; the node weight gradient runs beside them
@@ -338,6 +364,8 @@ static int validate_config(const cgr_gnn_config* c) {
   CGR_CHECK(c->pooling == CGR_POOL_ADD || c->pooling == CGR_POOL_MEAN ||
                 c->pooling == CGR_POOL_MAX,
             "cgr: unknown pooling (CGR_POOL_ADD, CGR_POOL_MEAN, CGR_POOL_MAX)");
+  CGR_CHECK(c->precision == CGR_PRECISION_SPLIT || c->precision == CGR_PRECISION_FP32,
+            "cgr: unknown precision (CGR_PRECISION_SPLIT, CGR_PRECISION_FP32)");
   return 0;
 }
 
@@ -460,7 +488,7 @@ int cgr_gnn_forward(const cgr_gnn_config* cfg, const float* const* params, const
   note_forward(arena, -1);  // not usable by a backward unless the forward below succeeds
   const int r = gnn_forward_impl(d, params, b, dropout_p, seed, rng_counter, training, arena, y,
                                  (hipStream_t)stream, FwdMode{});
-  if (r == 0) note_forward(arena, training);
+  if (r == 0) note_forward(arena, training, cfg->precision);
   return r;
 }
 
@@ -484,6 +512,9 @@ int cgr_gnn_backward(const cgr_gnn_config* cfg, const float* const* params, cons
             "CGR_TRAIN_FOR_BACKWARD set");
   CGR_CHECK((ff & CGR_TRAIN_DROPOUT) == (training & CGR_TRAIN_DROPOUT),
             "cgr_gnn_backward: `training` dropout bit differs from the forward's");
+  CGR_CHECK(forward_mode(arena) == cfg->precision,
+            "cgr_gnn_backward: the config's precision differs from the mode `arena`'s forward "
+            "ran in");
   const int np = cgr_gnn_num_params(cfg);
   for (int i = 0; i < np; ++i) {
     CGR_CHECK(params[i] != nullptr, "cgr: NULL parameter pointer");
@@ -514,6 +545,9 @@ int cgr_gnn_input_grads(const cgr_gnn_config* cfg, const float* const* params,
   CGR_CHECK(ff >= 0 && (ff & CGR_TRAIN_FOR_BACKWARD),
             "cgr_gnn_input_grads: `arena` was not filled by a successful cgr_gnn_forward with "
             "CGR_TRAIN_FOR_BACKWARD set");
+  CGR_CHECK(forward_mode(arena) == cfg->precision,
+            "cgr_gnn_input_grads: the config's precision differs from the mode `arena`'s forward "
+            "ran in");
   CGR_CHECK(backward_matches(arena, workspace),
             "cgr_gnn_input_grads: `workspace` does not hold a cgr_gnn_backward of this `arena`'s "
             "latest forward (run the backward first, with the same arena and workspace)");

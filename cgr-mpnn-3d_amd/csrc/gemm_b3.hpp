@@ -143,18 +143,23 @@ __device__ __forceinline__ void b3_mfma6x2(const b3_u4 (&a)[3], const b3_u4 (&b)
 struct B3Cols {
   int tiles, nf, nimg;
 };
-// the instantiated fragment counts per tile (launch_b3nt's switch)
-inline int b3_nf_snap(int nf) {
+// the instantiated fragment counts per tile (launch_b3nt's switch).  acc: the per-k-step
+// accumulation variant of the NT kernel (CGR_PRECISION_FP32) keeps a pair's step sums beside the
+// running sums, so its tiles stop at kB3AccMaxNf fragment columns (at 11 and 13 it spills)
+constexpr int kB3MaxNf = 13, kB3AccMaxNf = 8;
+inline int b3_nf_snap(int nf, bool acc = false) {
   static const int sizes[] = {1, 2, 3, 4, 6, 7, 8, 11, 13};
+  const int top = acc ? kB3AccMaxNf : kB3MaxNf;
   for (int s : sizes)
-    if (s >= nf) return s;
-  return 13;
+    if (s >= nf && s <= top) return s;
+  return top;
 }
-inline B3Cols b3_cols(int N) {
+inline B3Cols b3_cols(int N, bool acc = false) {
   const int nft = (N + 15) / 16;
-  const int tiles = (nft + 12) / 13;
+  const int top = acc ? kB3AccMaxNf : kB3MaxNf;
+  const int tiles = (nft + top - 1) / top;
   int nf = (nft + tiles - 1) / tiles;
-  nf = b3_nf_snap(nf);
+  nf = b3_nf_snap(nf, acc);
   return B3Cols{tiles, nf, tiles * nf * 16};
 }
 inline int b3_nk(int K) { return (K + B3_BK - 1) / B3_BK; }
@@ -281,7 +286,12 @@ struct B3NtShape {
 //   The last step (the tail) has nothing to stage: its load slots take the epilogue's addend.
 //   Epilogue: see the passes below -- whole-tile functor, merged apply + segment pass (layer
 //   forward), flat apply pass (other addend epilogues), one column group per thread (plain).
-template <int WAVES, int RF, int NF, bool NOMASK, class AL, class EP>
+//   ACC (CGR_PRECISION_FP32): per-k-step accumulation.  The matrix core aligns every product of
+//   an MFMA to its largest operand, the accumulator included, so the small pieces' products are
+//   rounded at the ulp of the running sum.  With ACC a step's six piece products of a fragment go
+//   into a zeroed accumulator (aligned to the step's own largest product) and one fp32 add folds
+//   the step sum into the running sum.  The default (false) is the code path without it.
+template <int WAVES, int RF, int NF, bool NOMASK, class AL, class EP, bool ACC = false>
 __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u4* __restrict__ Bimg,
                                                                int nimg, EP ep, int M, int N,
                                                                int K, int tiles_n) {
@@ -471,6 +481,9 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
     // the read-ahead is issued here, ahead of everything (else the scheduler fills each pair's
     // ds_read group with that pair's own reads and waits on them right away)
     __builtin_amdgcn_sched_barrier(0);
+    // ACC: the previous pair's step sums; their adds are issued behind this pair's MFMAs, so
+    // only two pairs' step sums are live
+    floatx4 carx[ACC ? RF : 1], cary[ACC ? RF : 1];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const int j = 2 * p;
@@ -484,10 +497,24 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
         rd(j + 1 + LDA);
         nrd += 3;
       }
+      if constexpr (ACC) {
 #pragma unroll
-      for (int i = 0; i < RF; ++i)
-        b3_mfma6x2(afc[i], bq[j % RING], bq[(j + 1) % RING], two, acc[i][j],
-                   acc[i][two ? j + 1 : j]);
+        for (int i = 0; i < RF; ++i) {
+          floatx4 x = floatx4{0.f, 0.f, 0.f, 0.f}, y = x;
+          b3_mfma6x2(afc[i], bq[j % RING], bq[(j + 1) % RING], two, x, y);
+          if (p > 0) {
+            acc[i][j - 2] += carx[i];
+            acc[i][j - 1] += cary[i];  // every pair but the last has two columns
+          }
+          carx[i] = x;
+          cary[i] = y;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < RF; ++i)
+          b3_mfma6x2(afc[i], bq[j % RING], bq[(j + 1) % RING], two, acc[i][j],
+                     acc[i][two ? j + 1 : j]);
+      }
       constexpr int MQ = 4 * RF;  // a third of a pair's MFMAs
       if constexpr (!TAIL) {
         // this pair's share of the load slots and of the B stores
@@ -527,6 +554,14 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
         if (two) b3_sgb<0x008>(MQ); else b3_sgb<0x008>(MQ / 2);
         b3_sgb<0x020>(nvm);
         if (two) b3_sgb<0x008>(2 * MQ); else b3_sgb<0x008>(MQ + MQ / 2);
+      }
+    }
+    if constexpr (ACC) {  // the last pair's step sums
+      constexpr int jl = 2 * (NP - 1);
+#pragma unroll
+      for (int i = 0; i < RF; ++i) {
+        acc[i][jl] += carx[i];
+        if constexpr (jl + 1 < NF) acc[i][jl + 1] += cary[i];
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -778,11 +813,11 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_b3nt_kernel(AL al, const b3_u
   CGR_STAMP_END((TILE ? 2 : 0) | (SEG ? 1 : 0) | (NF << 2) | (WAVES << 7));
 }
 
-template <int WAVES, int RF, int NF, bool NOMASK, class AL, class EP>
+template <int WAVES, int RF, int NF, bool NOMASK, bool ACC = false, class AL, class EP>
 inline hipError_t launch_b3nt_t(const AL& al, const b3_u4* Bimg, int nimg, const EP& ep, int M,
                                 int N, int K, int tiles_n, hipStream_t st) {
   using S = B3NtShape<WAVES, RF, NF>;
-  auto kern = gemm_b3nt_kernel<WAVES, RF, NF, NOMASK, AL, EP>;
+  auto kern = gemm_b3nt_kernel<WAVES, RF, NF, NOMASK, AL, EP, ACC>;
   static LdsLimit lim;
   // the dynamic bytes this launch asks for (a diagnostic build adds static LDS: stamps.hpp)
   const hipError_t e = lim.ensure(reinterpret_cast<const void*>(kern), (int)S::LDS_BYTES);
@@ -818,8 +853,8 @@ inline int b3nt_rows(int M, int N) { return b3nt_waves(M, N) == 8 ? 128 : 64; }
 // Images are packed in the tiling they are launched with (b3_job(..., cols)).
 constexpr int kB3Cus = 256;
 constexpr int kB3StepFixed = 6;
-inline B3Cols b3nt_cols(int M, int N) {
-  const B3Cols c0 = b3_cols(N);
+inline B3Cols b3nt_cols(int M, int N, bool acc = false) {
+  const B3Cols c0 = b3_cols(N, acc);
   const int bm = b3nt_rows(M, N);
   const int tm = (M + bm - 1) / bm;
   const int nft = (N + 15) / 16;
@@ -830,7 +865,7 @@ inline B3Cols b3nt_cols(int M, int N) {
   B3Cols best = c0;
   int bc = cost(c0);
   for (int nf = c0.nf - 1; nf >= 2; --nf) {
-    if (b3_nf_snap(nf) != nf) continue;
+    if (b3_nf_snap(nf, acc) != nf) continue;
     const int tiles = (nft + nf - 1) / nf;
     const B3Cols c{tiles, nf, tiles * nf * 16};
     const int k = cost(c);
@@ -847,18 +882,28 @@ inline bool b3nt_side_fits(int M, int N, const B3Cols& c, size_t lds) {
 }
 
 // C = A B^T with B given as its image (b3_pack of the same N, K in the column tiling c).
-// M, N, K > 0.
+// M, N, K > 0.  acc: the per-k-step accumulation variant (c from b3_cols / b3nt_cols(.., true)).
 template <class AL, class EP>
 inline hipError_t launch_b3nt(const AL& al, const b3_u4* Bimg, const B3Cols& c, const EP& ep,
-                              int M, int N, int K, hipStream_t st) {
+                              int M, int N, int K, hipStream_t st, bool acc = false) {
   if (M <= 0 || N <= 0) return hipSuccess;
-  if (c.tiles * c.nf * 16 != c.nimg || c.nimg < N || b3_nf_snap(c.nf) != c.nf)
+  if (c.tiles * c.nf * 16 != c.nimg || c.nimg < N || b3_nf_snap(c.nf, acc) != c.nf)
     return hipErrorInvalidValue;
   const bool w8 = b3nt_waves(M, N) == 8;
   // unmasked A when K % 4 == 0: every fetched float4 is either all-valid or past K (clamped to
   // finite in-bounds data, multiplied by the image's zero rows)
   auto go = [&](auto NFc) -> hipError_t {
     constexpr int NF = decltype(NFc)::value;
+    if (acc) {
+      if constexpr (NF <= kB3AccMaxNf) {
+        if (K % 4 == 0)
+          return w8 ? launch_b3nt_t<8, 1, NF, true, true>(al, Bimg, c.nimg, ep, M, N, K, c.tiles, st)
+                    : launch_b3nt_t<4, 1, NF, true, true>(al, Bimg, c.nimg, ep, M, N, K, c.tiles, st);
+        return w8 ? launch_b3nt_t<8, 1, NF, false, true>(al, Bimg, c.nimg, ep, M, N, K, c.tiles, st)
+                  : launch_b3nt_t<4, 1, NF, false, true>(al, Bimg, c.nimg, ep, M, N, K, c.tiles, st);
+      }
+      return hipErrorInvalidValue;
+    }
     if (K % 4 == 0)
       return w8 ? launch_b3nt_t<8, 1, NF, true>(al, Bimg, c.nimg, ep, M, N, K, c.tiles, st)
                 : launch_b3nt_t<4, 1, NF, true>(al, Bimg, c.nimg, ep, M, N, K, c.tiles, st);

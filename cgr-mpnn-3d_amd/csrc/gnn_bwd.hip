@@ -218,6 +218,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   };
   // main: ds = dzn W_n[:, F:] = diag(dy[graph]) act'(zn) (diag(wf) W_n[:, F:]) -- the row factor in
   // the epilogue, the column factor in the weight image (gnn_fwd.hip), act' in the A loader
+  const bool acc = d.nt_acc();  // the NT launches' kernel variant (the images' tilings follow d)
   auto readout_nt = [&]() -> int {
     ProfScope _p("gemm_nt_readout_bwd", st);
     const float* m = d.act == ACT_RELU ? fv.hn : fv.zn;
@@ -225,19 +226,19 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     if (max_pool) {  // ds = dzn W_n[:, F:] with dzn materialised (its per-element arg-max mask is
                      // no row / column factor); the image is unscaled (gnn_fwd.hip)
       const EpStoreRowScale ep{ds, Hp, N, H, nullptr, iv.node_graph, nullptr, fv.inv_deg};
-      HIP_RET(launch_b3nt(LdPlain<4>{dzn, Hp}, img, b3nt_cols(N, H), ep, N, H, H, st));
+      HIP_RET(launch_b3nt(LdPlain<4>{dzn, Hp}, img, readout_cols(d), ep, N, H, H, st, acc));
       return 0;
     }
     // (mean pooling: dy / graph count; mean aggregation: ds / in-degree, for dh_D = ds[dst])
     const EpStoreRowScale ep{ds, Hp, N, H, dy, iv.node_graph, fv.inv_cnt, fv.inv_deg};
-    const B3Cols rc = b3nt_cols(N, H);  // the image's tiling (gnn_fwd.hip)
+    const B3Cols rc = readout_cols(d);  // the image's tiling (gnn_fwd.hip)
     // the activation derivative in the A loader, specialised per activation (main-loop code)
     if (d.act == ACT_RELU)
-      HIP_RET(launch_b3nt(LdActGradT<ACT_RELU>{m, Hp, d.act}, img, rc, ep, N, H, H, st));
+      HIP_RET(launch_b3nt(LdActGradT<ACT_RELU>{m, Hp, d.act}, img, rc, ep, N, H, H, st, acc));
     else if (d.act == ACT_SILU)
-      HIP_RET(launch_b3nt(LdActGradT<ACT_SILU>{m, Hp, d.act}, img, rc, ep, N, H, H, st));
+      HIP_RET(launch_b3nt(LdActGradT<ACT_SILU>{m, Hp, d.act}, img, rc, ep, N, H, H, st, acc));
     else
-      HIP_RET(launch_b3nt(LdActGradT<-1>{m, Hp, d.act}, img, rc, ep, N, H, H, st));
+      HIP_RET(launch_b3nt(LdActGradT<-1>{m, Hp, d.act}, img, rc, ep, N, H, H, st, acc));
     return 0;
   };
   // capture order: fork, side work, then the main NT.  Enqueuing the NT first (the fork point
@@ -349,13 +350,13 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
                             EpLayerBwdSeg<false>{lb, dm, iv.dst_s, iv.dst_ptr, iv.src_list,
                                                  iv.src_ptr, dg, dgn, part, cnt, iv.status, E, H, N,
                                                  seg_cols, gcnt, ss->dev_err, spin, fv.inv_deg},
-                            E, H, H, st));
+                            E, H, H, st, acc));
       else
         HIP_RET(launch_b3nt(al, img, lcols,
                             EpLayerBwdSeg<true>{lb, dm, iv.dst_s, iv.dst_ptr, iv.src_list,
                                                 iv.src_ptr, dg, dgn, part, cnt, iv.status, E, H, N,
                                                 seg_cols, gcnt, ss->dev_err, spin, fv.inv_deg},
-                            E, H, H, st));
+                            E, H, H, st, acc));
     }
     if (fork_ev) HIP_RET(hipStreamWaitEvent(side, fork_ev, 0));
     {  // side: dW_l = dpre^T m_l, db_l = colsum(dpre); the previous weight gradient's slabs are

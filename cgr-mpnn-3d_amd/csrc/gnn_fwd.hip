@@ -54,17 +54,18 @@ hipError_t pack_forward_images(const Dims& d, const float* const* params, const 
   hipError_t e;
   if (F > 0) {
     b3_u4* ximg = reinterpret_cast<b3_u4*>(base + IL.b3x);
-    const B3Cols cx = b3_cols(2 * H);
+    const B3Cols cx = image_cols(d, 2 * H);
     if ((e = b3_pack_add(pj, B3PackJob{W0, F + Fe, 1, ximg, 0, H, H, F, cx.nimg, b3_nk(F)}, st)))
       return e;
     if ((e = b3_pack_add(pj, B3PackJob{Wn, F + H, 1, ximg, H, cx.nimg - H, H, F, cx.nimg,
                                        b3_nk(F)}, st)))
       return e;
   }
-  if ((e = b3_pack_add(pj, b3_job(Wn + F, F + H, 1, H, H, base + IL.b3rof), st))) return e;
+  const B3Cols ch = image_cols(d, H);
+  if ((e = b3_pack_add(pj, b3_job(Wn + F, F + H, 1, H, H, base + IL.b3rof, ch), st))) return e;
   for (int l = 0; l < D; ++l)
-    if ((e = b3_pack_add(pj, b3_job(params[CGR_PARAM_CONV_W(l)], H, 1, H, H, base + IL.b3lf[l]),
-                         st)))
+    if ((e = b3_pack_add(pj, b3_job(params[CGR_PARAM_CONV_W(l)], H, 1, H, H, base + IL.b3lf[l],
+                                    ch), st)))
       return e;
   return b3_pack(pj, st);
 }
@@ -106,11 +107,13 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
   std::lock_guard<std::mutex> ss_lock(ss->mu);
   const bool packs = !caller_images;
   // column tilings: the x-GEMM's and the readout GEMMs' grid-filling over this batch's N rows
-  // (b3nt_cols) for the images packed here, b3_cols for batch-independent caller images
-  // (cgr_gnn_pack_images); the layer GEMMs' layer_cols
-  const B3Cols xcols = caller_images ? b3_cols(2 * H) : b3nt_cols(N, 2 * H);
-  const B3Cols rcols = caller_images ? b3_cols(H) : b3nt_cols(N, H);
-  const B3Cols lcols = caller_images ? b3_cols(H) : layer_cols(d);
+  // (x_cols, readout_cols) for the images packed here, image_cols for batch-independent caller
+  // images (cgr_gnn_pack_images); the layer GEMMs' layer_cols -- all in d's precision mode, as
+  // is the kernel variant (acc) of every NT launch below
+  const bool acc = d.nt_acc();
+  const B3Cols xcols = caller_images ? image_cols(d, 2 * H) : x_cols(d);
+  const B3Cols rcols = caller_images ? image_cols(d, H) : readout_cols(d);
+  const B3Cols lcols = caller_images ? image_cols(d, H) : layer_cols(d);
   // small batches: the graph bookkeeping as the x-GEMM launch's extra workgroup (prep_one.hpp)
   // on a CU no tile takes -- the whole forward start on one queue, no fork / join (each costs
   // ~5-10 us in a captured graph); else graph_prep.hip's launches on the caller's stream beside
@@ -234,7 +237,8 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
     }
     hipError_t e = with_vec(vec_for(xa, ldx, F), [&](auto VX) {
       LdPlain<decltype(VX)::value> al{xa, ldx};
-      return launch_b3nt(al, static_cast<const b3_u4*>(fv.b3x), xcols, ep, N, 2 * H, Kx, side);
+      return launch_b3nt(al, static_cast<const b3_u4*>(fv.b3x), xcols, ep, N, 2 * H, Kx, side,
+                         acc);
     });
     HIP_RET(e);
   } else {
@@ -319,11 +323,11 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
       HIP_RET(launch_b3nt(al, img, lcols,
                           EpLayerSeg{ep, iv.dst_s, fv.a[l + 1], Hp, znext, iv.dst_ptr, iv.fpart,
                                      iv.fcnt, lcols.tiles},
-                          E, H, H, st));
+                          E, H, H, st, acc));
     } else {
       {
         ProfScope _p("gemm_nt_layer_fwd", st);
-        HIP_RET(launch_b3nt(al, img, lcols, ep, E, H, H, st));
+        HIP_RET(launch_b3nt(al, img, lcols, ep, E, H, H, st, acc));
       }
       ProfScope _p2("segsum_dst_fwd", st);
       HIP_RET(segment_sum(fv.h[l + 1], Hp, nullptr, iv.dst_ptr, N, Hp, fv.a[l + 1], Hp, st));
@@ -336,7 +340,7 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
     ProfScope _p("gemm_nt_readout_fwd", st);
     EpReadoutQ ep{bn, fv.Q, fv.hn, fv.zn, Hp, N, H, d.act};
     HIP_RET(launch_b3nt(LdPlain<4>{fv.a[D], Hp}, static_cast<const b3_u4*>(fv.b3rof), rcols, ep,
-                        N, H, H, st));
+                        N, H, H, st, acc));
   }
   ProfScope _p("pool_head_fwd", st);
   HIP_RET(pool_head_fwd(fv.hn, Hp, iv.graph_ptr, d.B, H, params[CGR_PARAM_FFN_W(D)],

@@ -97,6 +97,11 @@ struct Dims {
   int act;
   int learnable_skip;
   int aggr, pool;  // enum cgr_aggregation / cgr_pooling
+  // enum cgr_precision.  Every layout function and every launch decision reads the mode from
+  // here and nowhere else: the NT GEMMs' variant and column tilings (nt_acc: x_cols,
+  // readout_cols, layer_cols, image_cols) and the weight gradients' families (wgrad_candidates)
+  int precision;
+  bool nt_acc() const { return precision == CGR_PRECISION_FP32; }  // per-k-step accumulation
 };
 
 struct ArenaLayout {
@@ -144,7 +149,14 @@ inline int input_grad_ldw(int H) { return (2 * H + 3) & ~3; }
 int bwd_dsig_slots(const Dims& d);
 int bwd_seg_tiles(const Dims& d);
 struct B3Cols;
-B3Cols layer_cols(const Dims& d);  // column tiling of the layer GEMMs (capi.hip)
+// Column tilings of the NT GEMMs in d's precision mode (capi.hip): images are packed, sized and
+// launched in these.  layer: the layer GEMMs, forward and fused backward; x: the x-GEMM's
+// [P | Q]; readout: the node-row readout GEMMs, forward and backward; image: the
+// batch-independent tiling of caller-packed images (cgr_gnn_pack_images) over n columns.
+B3Cols layer_cols(const Dims& d);
+B3Cols x_cols(const Dims& d);
+B3Cols readout_cols(const Dims& d);
+B3Cols image_cols(const Dims& d, int n);
 
 // Forward variants.  Training (cgr_gnn_forward): every activation the backward reads is saved in
 // the arena and the weight images are packed into it by each call.  Eval (cgr_gnn_predict): no

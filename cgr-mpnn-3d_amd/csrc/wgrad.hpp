@@ -101,7 +101,12 @@ inline WgCandidates wgrad_candidates(WgSite s, const Dims& d) {
   const int64_t Hp = d.Hp;
   const int Fx = d.F % 4 ? d.Fp : d.F;
   WgCandidates w{};
-  auto add = [&](const WgChoice& c) { w.c[w.n++] = c; };
+  // CGR_PRECISION_FP32 leaves the split-bf16 family out at every site: the first feasible fp32
+  // family runs, on fp32 rows (bias riders included), and no e-image is written or sized
+  const bool fp32_only = d.precision == CGR_PRECISION_FP32;
+  auto add = [&](const WgChoice& c) {
+    if (!(fp32_only && c.family == WgFamily::B3)) w.c[w.n++] = c;
+  };
   switch (s) {
     case WgSite::Readout:
       add(wg_b3(LdConcat<4>{nullptr, Fx, nullptr, Hp, Fx}, H, Fx + H, N, kB3TnReadoutTarget, true));

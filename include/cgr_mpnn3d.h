@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CGR_ABI_VERSION 8
+#define CGR_ABI_VERSION 9
 #define CGR_MAX_DEPTH 32
 
 enum cgr_status {
@@ -59,7 +59,19 @@ typedef struct cgr_gnn_config {
   int32_t learnable_skip;    /* use_learnable_skip (GNN.py:71-74, :94-97) */
   int32_t aggregation;       /* enum cgr_aggregation: DMPNNConv(aggr=...) (GNN.py:22,63,119) */
   int32_t pooling;           /* enum cgr_pooling: pooling_fn (GNN.py:23,110) */
+  int32_t precision;         /* enum cgr_precision (ABI 9; no reference counterpart) */
 } cgr_gnn_config;
+
+/* Arithmetic of the GNN kernels.  CGR_PRECISION_SPLIT (the default): the split-bf16 NT GEMMs add
+ * every piece product into the matrix core's running sum, and widths up to 512 take their weight
+ * gradients from two-piece split-bf16 operands -- predictions within the reference's fp32 at 1e-4,
+ * some gradients outside it.  CGR_PRECISION_FP32: every 32-deep k step of an
+ * NT GEMM is summed on its own and folded into the running sum with one fp32 add, and every weight
+ * and bias gradient comes from fp32 rows on an fp32 TN kernel -- fp32-class against float64 at
+ * every stage, slower.  The mode is part of the config: sizes, offsets, the
+ * image layout of cgr_gnn_pack_images and every launch follow it, and cgr_gnn_backward /
+ * cgr_gnn_input_grads refuse a config whose mode differs from the one `arena`'s forward ran in. */
+enum cgr_precision { CGR_PRECISION_SPLIT = 0, CGR_PRECISION_FP32 = 1 };
 
 /* aggr of GNN.__init__ / DMPNNConv (PyG MessagePassing): "add" (= "sum", the default) or "mean"
  * (the sum over a node's in-edges divided by their count, 0 for a node without in-edges) */

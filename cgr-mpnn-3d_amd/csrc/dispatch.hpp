@@ -7,7 +7,9 @@
 //   gemm_tnr.hpp  register-direct fp32 TN (weight gradients of shapes the split TN does not cover)
 //   gemm.hpp      LDS-staged fp32 NT / TN (standalone DMPNNConv, the edge-feature weight gradient
 //                 with K = Fe = 14, and any remaining shape)
-// Which TN family a weight gradient takes, with which plan and workgroup target: wgrad.hpp (one
+// What the three share is in gemm.hpp: the row loaders (an operand is described once, as an Ld*
+// struct, whichever family reads it) and the weight gradients' plan type and split rule (TnPlan,
+// tn_split).  Which TN family a weight gradient takes, with which workgroup target: wgrad.hpp (one
 // table for the launch and for the slab sizing).
 #pragma once
 

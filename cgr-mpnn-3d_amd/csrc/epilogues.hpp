@@ -73,7 +73,7 @@ struct EpStorePermRows {
 };
 
 // C[r, :] = s_r * acc with s_r = dy[node_graph[r]] (readout backward ds = dzn W_n[:, F:], the
-// row factor of dzn; LdActGrad).  Internal [M, ld] buffers, ld % 4 == 0.
+// row factor of dzn; LdActGradT).  Internal [M, ld] buffers, ld % 4 == 0.
 // gscale / nscale (nullable): mean pooling's per-graph 1 / count, mean aggregation's per-node
 // 1 / in-degree (ds feeds dh_D = ds[dst] / deg(dst) only)
 struct EpStoreRowScale {

@@ -1,12 +1,18 @@
-// fp32 MFMA GEMM templates for the D-MPNN path (gfx950, v_mfma_f32_16x16x4_f32).
+// The row loaders every GEMM family reads its operands through, the one weight-gradient plan
+// type (TnPlan, tn_split) and the LDS-staged fp32 MFMA GEMMs (gfx950, v_mfma_f32_16x16x4_f32).
 //
-// Two shapes cover every GEMM of the forward and backward (SURVEY.md §2a K3,K7,K10 and their
-// backward):
+// Loaders (LdPlain, LdGatherRows, LdActGradT, LdGatherDiff, LdConcat) describe an operand once per
+// call site: this file's kernels call their row / fetch / combine, the split-bf16 GEMMs
+// (gemm_b3.hpp) and the register-direct TN (gemm_tnr.hpp) read the same structs through an
+// adapter beside their kernel (B3TnSrc<L>, TnrSrc<L>).
 //
-//   gemm_nt:  C[m, n] = sum_k A(m, k) * B(n, k)      A rows produced by a *loader* (plain rows,
-//             gathered a[src]-h[rev] rows, or the [x | s] concat), B = rows of a weight matrix
-//             ([out, in] = nn.Linear layout); an *epilogue* functor consumes C as float4 row
-//             pieces (bias / skip / activation / dropout / stores).
+// The LDS-staged kernels run the standalone DMPNNConv, the narrow input-gradient GEMMs, the
+// edge-feature weight gradient (K = Fe = 14) and every weight-gradient shape the other two
+// families do not cover (wgrad.hpp):
+//
+//   gemm_nt:  C[m, n] = sum_k A(m, k) * B(n, k)      A rows produced by a *loader*, B = rows of a
+//             weight matrix ([out, in] = nn.Linear layout); an *epilogue* functor consumes C as
+//             float4 row pieces (bias / skip / activation / dropout / stores).
 //   gemm_tn:  C[n, k] = sum_e A(e, n) * B(e, k)      weight gradients dW = dZ^T Q, reduction over
 //             the (long) edge / node dimension, split into row ranges with fp32 partial slabs
 //             (deterministic: reduce_slabs sums them in a fixed order).  Workgroups of k-tile 0
@@ -20,7 +26,9 @@
 //       one b128 read feeds four MFMAs.
 //   TN: e-major LDS tiles ([BE][BM + pad], stride == 16 mod 32 floats) read with conflict-free
 //       ds_read_b32; global loads stay coalesced float4 along n / k.
-//   Loads are software-pipelined one k-tile ahead through registers.  Loaders are BRANCH-FREE:
+//   Loads are software-pipelined through registers, two k-tiles ahead in the NT kernel and one
+//   row tile ahead in the TN kernel (distance 2 there measured slower in the step:
+//   tools/experiments/tn_prefetch_2.patch).  Loaders are BRANCH-FREE:
 //   fetch() issues every global load unconditionally from a clamped, in-bounds address and
 //   combine() applies masks / the a[src]-h[rev] subtraction when the tile is written to LDS, so
 //   the compiler's s_waitcnt vmcnt lands after the MFMAs instead of in front of them (with
@@ -97,13 +105,6 @@ struct LdPlain {
   // no masks (K % 4 == 0, finite data: rows past the end and k >= K read finite in-bounds
   // elements whose products meet zero weights or are discarded by the epilogue)
   __device__ __forceinline__ float4 combine_nm(const Raw& v) const { return v; }
-  typedef float Raw1;  // single element k (column-blocked staging of the split-bf16 TN kernel)
-  __device__ __forceinline__ Raw1 fetch1(const Row& rw, int k, int K) const {
-    return rw.p[k < K ? k : 0];
-  }
-  __device__ __forceinline__ float combine1(Raw1 v, const Row& rw, int k, int K) const {
-    return (rw.ok && k < K) ? v : 0.f;
-  }
 };
 
 // rows gathered through an index: A(r, :) = base[idx[r], :]  (internal buffers, ld % 4 == 0).
@@ -144,7 +145,6 @@ struct LdActGradT {
     const float* p;
     bool ok;
   };
-using LdActGrad = LdActGradT<-1>;
   typedef float4 Raw;
   __device__ __forceinline__ Row row(int r, int limit) const {
     const bool ok = r < limit;
@@ -160,43 +160,6 @@ using LdActGrad = LdActGradT<-1>;
   }
   __device__ __forceinline__ float4 combine(const Raw& v, const Row& rw, int k, int K) const {
     return mask4(combine_nm(v), rw.ok, k, K);
-  }
-};
-
-// B rows of two stacked weight matrices: rows [0, n0) from base0 (ld0), rows [n0, ...) from base1
-// (ld1).  Used for the merged x-GEMM  x @ [W0[:, :F]; W_n[:, :F]]^T.  VEC divides ld0, ld1, K.
-template <int VEC>
-struct LdTwoRows {
-  const float* base0;
-  int64_t ld0;
-  const float* base1;
-  int64_t ld1;
-  int n0;
-  struct Row {
-    const float* p;
-    bool ok;
-  };
-  typedef float4 Raw;
-  __device__ __forceinline__ Row row(int r, int limit) const {
-    const bool ok = r < limit;
-    const int rr = ok ? r : 0;
-    return Row{rr < n0 ? base0 + (int64_t)rr * ld0 : base1 + (int64_t)(rr - n0) * ld1, ok};
-  }
-  __device__ __forceinline__ Raw fetch(const Row& rw, int k, int K) const {
-    return fetch4<VEC>(rw.p, k, K);
-  }
-  __device__ __forceinline__ float4 combine(const Raw& v, const Row& rw, int k, int K) const {
-    return mask4(v, rw.ok, k, K);
-  }
-  // no masks (K % 4 == 0, finite data: rows past the end and k >= K read finite in-bounds
-  // elements whose products meet zero weights or are discarded by the epilogue)
-  __device__ __forceinline__ float4 combine_nm(const Raw& v) const { return v; }
-  typedef float Raw1;  // single element k (column-blocked staging of the split-bf16 TN kernel)
-  __device__ __forceinline__ Raw1 fetch1(const Row& rw, int k, int K) const {
-    return rw.p[k < K ? k : 0];
-  }
-  __device__ __forceinline__ float combine1(Raw1 v, const Row& rw, int k, int K) const {
-    return (rw.ok && k < K) ? v : 0.f;
   }
 };
 
@@ -231,16 +194,6 @@ struct LdGatherDiff {
     return mask4(f4sub(v.a, v.h), rw.ok, k, K);
   }
   __device__ __forceinline__ float4 combine_nm(const Raw& v) const { return f4sub(v.a, v.h); }
-  struct Raw1 {
-    float a, h;
-  };
-  __device__ __forceinline__ Raw1 fetch1(const Row& rw, int k, int K) const {
-    const int kk = k < K ? k : 0;
-    return Raw1{a[(int64_t)rw.s * ld + kk], h[(int64_t)rw.r * ld + kk]};
-  }
-  __device__ __forceinline__ float combine1(const Raw1& v, const Row& rw, int k, int K) const {
-    return (rw.ok && k < K) ? v.a - v.h : 0.f;
-  }
 };
 
 // q[v, :] = [x[v, :F] | s[v, :H]]  (GNN.py:106).  VEC divides F and ldx (so no VEC sub-chunk
@@ -291,13 +244,6 @@ struct LdConcat {
   // no masks (K % 4 == 0, finite data: rows past the end and k >= K read finite in-bounds
   // elements whose products meet zero weights or are discarded by the epilogue)
   __device__ __forceinline__ float4 combine_nm(const Raw& v) const { return v; }
-  typedef float Raw1;  // single element k (column-blocked staging of the split-bf16 TN kernel)
-  __device__ __forceinline__ Raw1 fetch1(const Row& rw, int k, int K) const {
-    return *(k < F ? rw.px + k : (k < K ? rw.ps + (k - F) : rw.px));
-  }
-  __device__ __forceinline__ float combine1(Raw1 v, const Row& rw, int k, int K) const {
-    return (rw.ok && k < K) ? v : 0.f;
-  }
 };
 
 // ------------------------------------------------------------------------------------------
@@ -321,10 +267,9 @@ struct NTShape {
 // the next tile's global loads spread over the MFMAs, one per kNtIl (lab: layer NT gather 65.7 ->
 // 59.0 us, plain 58.3 -> 53.8; step A/B -2 %; 4: -1.5 %)
 constexpr int kNtIl = 5;
-// OCC > 0 asks the compiler for OCC waves per SIMD (register budget 512 / OCC per lane)
-template <int WAVES, int RM, int RN, int KT, int PF, int OCC, class AL, class BL, class EP>
+template <int WAVES, int RM, int RN, int KT, class AL, class BL, class EP>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, WAVES * 64),
-                          amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) void
+                          amdgpu_waves_per_eu(1))) void
 gemm_nt_kernel(AL al, BL bl, EP ep, int M, int N, int K, int tiles_n) {
   using S = NTShape<WAVES, RM, RN, KT>;
   constexpr int NT = S::NT, BM = S::BM, BN = S::BN, BK = S::BK, CPR = S::CPR;
@@ -409,62 +354,47 @@ gemm_nt_kernel(AL al, BL bl, EP ep, int M, int N, int K, int tiles_n) {
     }
   };
 
-  if constexpr (PF == 1) {
-    fetch(ra, rb, 0);
-    sstore(ra, rb, 0, 0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      const bool more = kt + 1 < nk;
-      const int kb = (kt + 1) * BK;
-      if (more) fetch(ra, rb, kb);
-      compute(cur);
-      if (more) sstore(ra, rb, cur ^ 1, kb);
-      __syncthreads();
-    }
-  } else {
-    // prefetch distance 2: the global loads of tile t+2 are issued before tile t is computed and
-    // consumed (written to LDS) only at the end of iteration t+1, so each load has two
-    // iterations of MFMA work to land.  Register sets alternate by tile parity (loop unrolled
-    // by 2 so they stay static); two LDS buffers suffice because a buffer is rewritten only
-    // after the barrier that ends its readers' iteration.
-    // Fetches are unconditional (tiles past K read in-bounds addresses and are zero-masked by
-    // combine), so no branch separates a load from its consumer and the waitcnt pass can count.
-    typename AL::Raw ra2[APT];
-    typename BL::Raw rb2[BPT];
-    fetch(ra, rb, 0);
-    fetch(ra2, rb2, BK);
-    sstore(ra, rb, 0, 0);
-    __syncthreads();
-    int kt = 0;
-    // the loads of tile t+2 are spread over tile t's MFMAs (one per kNtIl) instead of issued as
-    // one burst ahead of them
-    auto il = [&]() {
-      __builtin_amdgcn_sched_group_barrier(0x100, KT * (RM + RN), 0);  // fragment ds_reads
+  // prefetch distance 2: the global loads of tile t+2 are issued before tile t is computed and
+  // consumed (written to LDS) only at the end of iteration t+1, so each load has two
+  // iterations of MFMA work to land.  Register sets alternate by tile parity (loop unrolled
+  // by 2 so they stay static); two LDS buffers suffice because a buffer is rewritten only
+  // after the barrier that ends its readers' iteration.
+  // Fetches are unconditional (tiles past K read in-bounds addresses and are zero-masked by
+  // combine), so no branch separates a load from its consumer and the waitcnt pass can count.
+  typename AL::Raw ra2[APT];
+  typename BL::Raw rb2[BPT];
+  fetch(ra, rb, 0);
+  fetch(ra2, rb2, BK);
+  sstore(ra, rb, 0, 0);
+  __syncthreads();
+  int kt = 0;
+  // the loads of tile t+2 are spread over tile t's MFMAs (one per kNtIl) instead of issued as
+  // one burst ahead of them
+  auto il = [&]() {
+    __builtin_amdgcn_sched_group_barrier(0x100, KT * (RM + RN), 0);  // fragment ds_reads
 #pragma unroll
-      for (int q = 0; q < APT * (sizeof(typename AL::Raw) / 16) + BPT; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x008, kNtIl, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-      }
-    };
-    for (; kt + 2 <= nk; kt += 2) {  // buf 0 holds tile kt, set 2 holds tile kt + 1
-      fetch(ra, rb, (kt + 2) * BK);
-      compute(0);
-      il();
-      __builtin_amdgcn_sched_barrier(0);
-      sstore(ra2, rb2, 1, (kt + 1) * BK);
-      __syncthreads();
-      fetch(ra2, rb2, (kt + 3) * BK);
-      compute(1);
-      il();
-      __builtin_amdgcn_sched_barrier(0);
-      sstore(ra, rb, 0, (kt + 2) * BK);
-      __syncthreads();
+    for (int q = 0; q < APT * (sizeof(typename AL::Raw) / 16) + BPT; ++q) {
+      __builtin_amdgcn_sched_group_barrier(0x008, kNtIl, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
     }
-    if (kt < nk) {
-      compute(0);
-      __syncthreads();  // the epilogue reuses the stage buffers
-    }
+  };
+  for (; kt + 2 <= nk; kt += 2) {  // buf 0 holds tile kt, set 2 holds tile kt + 1
+    fetch(ra, rb, (kt + 2) * BK);
+    compute(0);
+    il();
+    __builtin_amdgcn_sched_barrier(0);
+    sstore(ra2, rb2, 1, (kt + 1) * BK);
+    __syncthreads();
+    fetch(ra2, rb2, (kt + 3) * BK);
+    compute(1);
+    il();
+    __builtin_amdgcn_sched_barrier(0);
+    sstore(ra, rb, 0, (kt + 2) * BK);
+    __syncthreads();
+  }
+  if (kt < nk) {
+    compute(0);
+    __syncthreads();  // the epilogue reuses the stage buffers
   }
 
   // epilogue: accumulators -> LDS [BM][LDC] -> coalesced float4 rows -> ep.apply4p.  Every
@@ -502,13 +432,13 @@ gemm_nt_kernel(AL al, BL bl, EP ep, int M, int N, int K, int tiles_n) {
   }
 }
 
-template <int WAVES, int RM, int RN, int KT, class AL, class BL, class EP, int PF = 2, int OCC = 0>
+template <int WAVES, int RM, int RN, int KT, class AL, class BL, class EP>
 inline hipError_t launch_gemm_nt(const AL& al, const BL& bl, const EP& ep, int M, int N, int K,
                                  hipStream_t st) {
   using S = NTShape<WAVES, RM, RN, KT>;
   if (M <= 0 || N <= 0) return hipSuccess;
   const int tm = (M + S::BM - 1) / S::BM, tn = (N + S::BN - 1) / S::BN;
-  hipLaunchKernelGGL((gemm_nt_kernel<WAVES, RM, RN, KT, PF, OCC, AL, BL, EP>), dim3(tm * tn),
+  hipLaunchKernelGGL((gemm_nt_kernel<WAVES, RM, RN, KT, AL, BL, EP>), dim3(tm * tn),
                      dim3(WAVES * 64), 0, st, al, bl, ep, M, N, K, tn);
   return hipGetLastError();
 }
@@ -516,9 +446,27 @@ inline hipError_t launch_gemm_nt(const AL& al, const BL& bl, const EP& ep, int M
 // ------------------------------------------------------------------------------------------
 // TN split-K GEMM (weight gradients)
 // ------------------------------------------------------------------------------------------
+// The plan of a weight gradient on any of the three TN families (this file, gemm_tnr.hpp,
+// gemm_b3.hpp): tiles_n x tiles_k output tiles, each over `splits` ranges of rows_per_split rows;
+// the grid is their product, the slabs are [splits][Nout][round_up(Kout, 4)] (bias [splits][Nout]).
 struct TnPlan {
   int tiles_n, tiles_k, splits, rows_per_split;
 };
+// The split rule the families share; each brings its own min_rows and granule.
+//   floor(target / tiles) splits -- floor, not ceil: the grid must not exceed the target (a whole
+//   number of workgroups per CU); one workgroup past it puts an extra one on a few CUs, and those
+//   CUs set the kernel's time -- capped so that a split keeps at least min_rows rows; rows per
+//   split rounded up to the granule, and the split count recomputed from that.
+inline void tn_split(TnPlan& p, int R, int tiles, int target_wgs, int min_rows, int granule) {
+  int splits = target_wgs / tiles;
+  const int max_splits = (R + min_rows - 1) / min_rows;
+  if (splits > max_splits) splits = max_splits;
+  if (splits < 1) splits = 1;
+  int rps = (R + splits - 1) / splits;
+  rps = (rps + granule - 1) / granule * granule;
+  p.splits = R > 0 ? (R + rps - 1) / rps : 1;
+  p.rows_per_split = rps;
+}
 
 template <int WAVES, int RM, int RN, int KT>
 struct TNShape {
@@ -536,7 +484,7 @@ struct TNShape {
   static_assert(ACH % NT == 0, "A chunks per thread must be integral");
 };
 
-template <int WAVES, int RM, int RN, int KT, class AL, class BL, int PF>
+template <int WAVES, int RM, int RN, int KT, class AL, class BL>
 __global__ __launch_bounds__(WAVES * 64) void gemm_tn_kernel(
     AL al, BL bl, float* __restrict__ slab, float* __restrict__ bslab, int Nout, int Kout, int R,
     int rows_per_split, int tiles_k, int want_bias) {
@@ -649,61 +597,25 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_tn_kernel(
     }
   };
 
-  if constexpr (PF == 1) {
-    Set x;
-    if (nt > 0) {
-      mkrows(0);
-      fetch(x);
-      mkrows(1);
-      sstore(x, 0);
-    }
-    __syncthreads();
-    for (int t = 0; t < nt; ++t) {
-      const int cur = t & 1;
-      const bool more = t + 1 < nt;
-      if (more) {
-        fetch(x);       // tile t+1, rows prepared during the previous iteration
-        mkrows(t + 2);  // index loads for tile t+2
-      }
-      compute(cur);
-      if (more) sstore(x, cur ^ 1);
-      __syncthreads();
-    }
-  } else if (nt > 0) {
-    // prefetch distance 2: tile t+2 is fetched before tile t is computed and written to LDS at
-    // the end of iteration t+1.  Fetches are unconditional (rows past e_end read row 0, masked by
-    // combine), so no branch separates a load from its consumer; register sets alternate by tile
-    // parity (loop unrolled by 2).
-    Set x0, x1;
+  // prefetch distance 1: tile t+1 is fetched before tile t is computed and written to the other
+  // LDS buffer after it
+  Set x;
+  if (nt > 0) {
     mkrows(0);
-    fetch(x0);
+    fetch(x);
     mkrows(1);
-    fetch(x1);
-    mkrows(2);
-    sstore(x0, 0);
-    __syncthreads();
-    int t = 0;
-    for (; t + 2 <= nt; t += 2) {
-      fetch(x0);  // tile t+2
-      mkrows(t + 3);
-      __builtin_amdgcn_sched_barrier(0);
-      compute(0);
-      __builtin_amdgcn_sched_barrier(0);
-      sstore(x1, 1);  // tile t+1 (t + 1 < nt here)
-      __syncthreads();
-      fetch(x1);  // tile t+3
-      mkrows(t + 4);
-      __builtin_amdgcn_sched_barrier(0);
-      compute(1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (t + 2 < nt) sstore(x0, 0);  // tile t+2
-      __syncthreads();
+    sstore(x, 0);
+  }
+  __syncthreads();
+  for (int t = 0; t < nt; ++t) {
+    const int cur = t & 1;
+    const bool more = t + 1 < nt;
+    if (more) {
+      fetch(x);       // tile t+1, rows prepared during the previous iteration
+      mkrows(t + 2);  // index loads for tile t+2
     }
-    if (t < nt) {
-      compute(0);
-      __syncthreads();
-    }
-  } else {
+    compute(cur);
+    if (more) sstore(x, cur ^ 1);
     __syncthreads();
   }
 
@@ -736,27 +648,16 @@ inline TnPlan plan_tn(int Nout, int Kout, int R, int target_wgs) {
   TnPlan p;
   p.tiles_n = (Nout + S::BM - 1) / S::BM;
   p.tiles_k = (Kout + S::BN - 1) / S::BN;
-  const int tiles = p.tiles_n * p.tiles_k;
-  // floor, not ceil: the grid must not exceed the target (a whole number of workgroups per CU);
-  // one workgroup past it puts an extra one on a few CUs, and those CUs set the kernel's time
-  int splits = target_wgs / tiles;
-  const int max_splits = (R + 4 * S::BE - 1) / (4 * S::BE);  // >= 4 k-tiles per split
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int rps = (R + splits - 1) / splits;
-  rps = (rps + S::BE - 1) / S::BE * S::BE;
-  p.splits = R > 0 ? (R + rps - 1) / rps : 1;
-  p.rows_per_split = rps;
+  // >= 4 row tiles per split, splits start on tile boundaries
+  tn_split(p, R, p.tiles_n * p.tiles_k, target_wgs, 4 * S::BE, S::BE);
   return p;
 }
 
-// TN prefetch distance (2: same-box A/B +1 % step time, layer wgrad slower, node/readout faster)
-constexpr int kTnPf = 1;
-template <int WAVES, int RM, int RN, int KT, class AL, class BL, int PF = kTnPf>
+template <int WAVES, int RM, int RN, int KT, class AL, class BL>
 inline hipError_t launch_gemm_tn(const AL& al, const BL& bl, const TnPlan& p, float* slab,
                                  float* bslab, int Nout, int Kout, int R, bool want_bias,
                                  hipStream_t st) {
-  hipLaunchKernelGGL((gemm_tn_kernel<WAVES, RM, RN, KT, AL, BL, PF>),
+  hipLaunchKernelGGL((gemm_tn_kernel<WAVES, RM, RN, KT, AL, BL>),
                      dim3(p.tiles_n * p.tiles_k * p.splits), dim3(WAVES * 64), 0, st, al, bl, slab,
                      bslab, Nout, Kout, R, p.rows_per_split, p.tiles_k, want_bias ? 1 : 0);
   return hipGetLastError();

@@ -944,24 +944,15 @@ namespace cgr {
 // below) takes A pre-split as an e-image and stages B transposed into LDS in the NT image
 // geometry ([piece][column row][4 swizzled 16-byte chunks of 8 e-rows]: every fragment read one
 // conflict-free ds_read_b128; column c stored at row sigma(c), a rotation inside its 16-column
-// block, so a b128 store pass hits four 64-byte bank groups).  Plans: one workgroup per (split of
-// the e rows, k-tile of TNK fragments), all Nout columns (TNN n-fragments) per workgroup; splits
-// start on 32-row boundaries.
-struct B3TnPlan {
-  int tiles_k, splits, rows_per_split, tnn;
-};
-inline B3TnPlan plan_b3tn(int Nout, int Kout, int R, int tnk, int target_wgs) {
-  B3TnPlan p;
-  p.tnn = (Nout + 15) / 16;
+// block, so a b128 store pass hits four 64-byte bank groups).  Plans (TnPlan, gemm.hpp): one
+// workgroup per (split of the e rows, k-tile of tnk fragments), all Nout columns per workgroup
+// (tiles_n = 1; the launcher takes the n-fragment count from Nout); at least 2 steps (64 rows) per
+// split, splits start on 32-row boundaries.
+inline TnPlan plan_b3tn(int Kout, int R, int tnk, int target_wgs) {
+  TnPlan p;
+  p.tiles_n = 1;
   p.tiles_k = (Kout + 16 * tnk - 1) / (16 * tnk);
-  int splits = target_wgs / p.tiles_k;
-  const int max_splits = (R + 63) / 64;  // >= 2 steps per split
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int rps = (R + splits - 1) / splits;
-  rps = (rps + 31) / 32 * 32;
-  p.splits = R > 0 ? (R + rps - 1) / rps : 1;
-  p.rows_per_split = rps;
+  tn_split(p, R, p.tiles_k, target_wgs, 64, 32);
   return p;
 }
 
@@ -1037,8 +1028,8 @@ inline int b3tn_tnk(int Nout) { return (Nout + 15) / 16 > 25 ? 4 : 5; }
 // workgroups of the layer weight gradient (A/B in the step: 128 -0.8 %, 256 -1.1 % vs 176; the
 // side stream shares the GPU with the main chain, fewer splits = smaller slabs)
 constexpr int kB3TnTarget = 176;
-inline B3TnPlan b3tn_plan(int Nout, int Kout, int R, int target = kB3TnTarget) {
-  return plan_b3tn(Nout, Kout, R, b3tn_tnk(Nout), target);
+inline TnPlan b3tn_plan(int Nout, int Kout, int R, int target = kB3TnTarget) {
+  return plan_b3tn(Kout, R, b3tn_tnk(Nout), target);
 }
 // ------------------------------------------------------------------------------------------
 // TN with the n-side operand as a pre-split e-image (weight gradients dW = A^T B whose A is
@@ -1386,7 +1377,7 @@ __global__ __launch_bounds__((B3TniShape<TNN, TNK>::NT)) void gemm_b3tni_kernel(
 
 // splits of the e-image TN: rows_per_split a multiple of 32 (plan_b3tn rounds it)
 template <int TNN, int TNK, class BL>
-inline hipError_t launch_b3tni_t(const B3EImg& ai, const BL& bl, const B3TnPlan& p, float* slab,
+inline hipError_t launch_b3tni_t(const B3EImg& ai, const BL& bl, const TnPlan& p, float* slab,
                                  float* bslab, int Nout, int Kout, int R, bool want_bias,
                                  hipStream_t st, const RedJob& prev) {
   using S = B3TniShape<TNN, TNK>;
@@ -1409,29 +1400,22 @@ inline bool b3tni_ok(const BL& bl, int Nout, int R) {
 }
 
 template <class BL>
-inline hipError_t launch_b3tni(const B3EImg& ai, const BL& bl, const B3TnPlan& p, float* slab,
+inline hipError_t launch_b3tni(const B3EImg& ai, const BL& bl, const TnPlan& p, float* slab,
                                float* bslab, int Nout, int Kout, int R, bool want_bias,
                                hipStream_t st, const RedJob& prev = RedJob{}) {
   constexpr int TNK = 5;
   if (!b3tni_ok(bl, Nout, R) || p.rows_per_split % 32) return hipErrorInvalidValue;
   if (p.tiles_k != (Kout + 16 * b3tn_tnk(Nout) - 1) / (16 * b3tn_tnk(Nout)))
     return hipErrorInvalidValue;  // a plan from b3tn_plan
-  switch (p.tnn) {
-    case 25: return launch_b3tni_t<25, TNK>(ai, bl, p, slab, bslab, Nout, Kout, R, want_bias, st, prev);
-    case 32: return launch_b3tni_t<32, 4>(ai, bl, p, slab, bslab, Nout, Kout, R, want_bias, st, prev);
-    default: break;
-  }
-  // other widths: the smallest instantiated fragment count that covers Nout (extra fragments
-  // read the image's zero columns and are not stored)
-  const int t = p.tnn;
-  B3TnPlan q = p;
-  if (t <= 2) { q.tnn = 2; return launch_b3tni_t<2, TNK>(ai, bl, q, slab, bslab, Nout, Kout, R, want_bias, st, prev); }
-  if (t <= 4) { q.tnn = 4; return launch_b3tni_t<4, TNK>(ai, bl, q, slab, bslab, Nout, Kout, R, want_bias, st, prev); }
-  if (t <= 8) { q.tnn = 8; return launch_b3tni_t<8, TNK>(ai, bl, q, slab, bslab, Nout, Kout, R, want_bias, st, prev); }
-  if (t <= 16) { q.tnn = 16; return launch_b3tni_t<16, TNK>(ai, bl, q, slab, bslab, Nout, Kout, R, want_bias, st, prev); }
-  if (t <= 25) { q.tnn = 25; return launch_b3tni_t<25, TNK>(ai, bl, q, slab, bslab, Nout, Kout, R, want_bias, st, prev); }
-  q.tnn = 32;
-  return launch_b3tni_t<32, 4>(ai, bl, q, slab, bslab, Nout, Kout, R, want_bias, st, prev);
+  // the smallest instantiated fragment count that covers Nout (25 at H = 400 and 32 at H = 512
+  // exactly; extra fragments read the image's zero columns and are not stored)
+  const int t = (Nout + 15) / 16;
+  if (t <= 2) return launch_b3tni_t<2, TNK>(ai, bl, p, slab, bslab, Nout, Kout, R, want_bias, st, prev);
+  if (t <= 4) return launch_b3tni_t<4, TNK>(ai, bl, p, slab, bslab, Nout, Kout, R, want_bias, st, prev);
+  if (t <= 8) return launch_b3tni_t<8, TNK>(ai, bl, p, slab, bslab, Nout, Kout, R, want_bias, st, prev);
+  if (t <= 16) return launch_b3tni_t<16, TNK>(ai, bl, p, slab, bslab, Nout, Kout, R, want_bias, st, prev);
+  if (t <= 25) return launch_b3tni_t<25, TNK>(ai, bl, p, slab, bslab, Nout, Kout, R, want_bias, st, prev);
+  return launch_b3tni_t<32, 4>(ai, bl, p, slab, bslab, Nout, Kout, R, want_bias, st, prev);
 }
 
 }  // namespace cgr

@@ -14,6 +14,10 @@
 // of e; the 4 waves take interleaved 4-row steps of the split and their partial tiles are combined
 // through LDS in a fixed order ((w0 + w1) + (w2 + w3)) before the split's fp32 slab is written
 // (same slab layout as gemm_tn_kernel, so reduce_slabs is shared).  Deterministic.
+//
+// Operands are the loaders of gemm.hpp (LdPlain, LdConcat, LdGatherDiff), the same objects the
+// other two TN families take; how this kernel reads one is TnrSrc<L>, below.  Plans are TnPlan
+// (gemm.hpp) by the shared split rule: at least 64 rows per split, 16-row granule (plan_tnr).
 #pragma once
 
 #include "common.hpp"
@@ -39,49 +43,55 @@ __device__ __forceinline__ void tnr_ld(const float* __restrict__ p, float (&v)[F
   }
 }
 
-// plain rows: value(e, c) = p[e * ld + c]
-struct TnrRows {
-  const float* p;
-  int64_t ld;
+// Per operand kind (the loaders of gemm.hpp, described once per call site): idx() loads the row
+// indices of row e (the gather's), fetch() issues the loads of F consecutive columns from c,
+// combine() forms their fp32 values.  Rows and columns are in bounds (the kernel clamps them).
+template <class L>
+struct TnrSrc;
+// plain rows: value(e, c) = base[e * ld + c]
+template <int V>
+struct TnrSrc<LdPlain<V>> {
   struct Idx {};
-  __device__ __forceinline__ Idx idx(int) const { return Idx{}; }
+  static __device__ __forceinline__ Idx idx(const LdPlain<V>&, int) { return Idx{}; }
   template <int F>
   struct Raw {
     float v[F];
   };
   template <int F>
-  __device__ __forceinline__ void fetch(int e, const Idx&, int c, Raw<F>& r) const {
-    tnr_ld<F>(p + (int64_t)e * ld + c, r.v);
+  static __device__ __forceinline__ void fetch(const LdPlain<V>& l, int e, const Idx&, int c,
+                                               Raw<F>& r) {
+    tnr_ld<F>(l.base + (int64_t)e * l.ld + c, r.v);
   }
   template <int F>
-  __device__ __forceinline__ void combine(const Raw<F>& r, float (&v)[F]) const {
+  static __device__ __forceinline__ void combine(const LdPlain<V>&, const Raw<F>& r,
+                                                 float (&v)[F]) {
 #pragma unroll
     for (int i = 0; i < F; ++i) v[i] = r.v[i];
   }
 };
 
 // message rows of a layer: value(e, c) = a[src[e], c] - h[rev[e], c]   (GNN.py:136-141)
-struct TnrDiff {
-  const float* a;
-  const float* h;
-  const int* src;
-  const int* rev;
-  int64_t ld;
+template <bool X>
+struct TnrSrc<LdGatherDiff<X>> {
   struct Idx {
     int s, r;
   };
-  __device__ __forceinline__ Idx idx(int e) const { return Idx{src[e], rev[e]}; }
+  static __device__ __forceinline__ Idx idx(const LdGatherDiff<X>& l, int e) {
+    return Idx{l.src[e], X ? (e ^ 1) : l.rev[e]};
+  }
   template <int F>
   struct Raw {
     float va[F], vh[F];
   };
   template <int F>
-  __device__ __forceinline__ void fetch(int, const Idx& x, int c, Raw<F>& r) const {
-    tnr_ld<F>(a + (int64_t)x.s * ld + c, r.va);
-    tnr_ld<F>(h + (int64_t)x.r * ld + c, r.vh);
+  static __device__ __forceinline__ void fetch(const LdGatherDiff<X>& l, int, const Idx& x, int c,
+                                               Raw<F>& r) {
+    tnr_ld<F>(l.a + (int64_t)x.s * l.ld + c, r.va);
+    tnr_ld<F>(l.h + (int64_t)x.r * l.ld + c, r.vh);
   }
   template <int F>
-  __device__ __forceinline__ void combine(const Raw<F>& r, float (&v)[F]) const {
+  static __device__ __forceinline__ void combine(const LdGatherDiff<X>&, const Raw<F>& r,
+                                                 float (&v)[F]) {
 #pragma unroll
     for (int i = 0; i < F; ++i) v[i] = r.va[i] - r.vh[i];
   }
@@ -89,41 +99,37 @@ struct TnrDiff {
 
 // [x | s] rows of the readout (GNN.py:106): value(e, c) = c < F ? x[e, c] : s[e, c - F]; F % 4 == 0
 // (x padded to 16-byte rows), so a lane's run of FB <= 4 columns never straddles the seam
-struct TnrConcat {
-  const float* x;
-  int64_t ldx;
-  const float* s;
-  int64_t lds;
-  int F;
+template <int V>
+struct TnrSrc<LdConcat<V>> {
   struct Idx {};
-  __device__ __forceinline__ Idx idx(int) const { return Idx{}; }
+  static __device__ __forceinline__ Idx idx(const LdConcat<V>&, int) { return Idx{}; }
   template <int F_>
   struct Raw {
     float v[F_];
   };
   template <int F_>
-  __device__ __forceinline__ void fetch(int e, const Idx&, int c, Raw<F_>& r) const {
-    tnr_ld<F_>(c < F ? x + (int64_t)e * ldx + c : s + (int64_t)e * lds + (c - F), r.v);
+  static __device__ __forceinline__ void fetch(const LdConcat<V>& l, int e, const Idx&, int c,
+                                               Raw<F_>& r) {
+    tnr_ld<F_>(c < l.F ? l.x + (int64_t)e * l.ldx + c : l.s + (int64_t)e * l.lds + (c - l.F), r.v);
   }
   template <int F_>
-  __device__ __forceinline__ void combine(const Raw<F_>& r, float (&v)[F_]) const {
+  static __device__ __forceinline__ void combine(const LdConcat<V>&, const Raw<F_>& r,
+                                                 float (&v)[F_]) {
 #pragma unroll
     for (int i = 0; i < F_; ++i) v[i] = r.v[i];
   }
-};
-
-struct TnrPlan {
-  int tiles_n, tiles_k, splits, rows_per_split;
 };
 
 constexpr int TNR_WAVES = 4;
 // data loads 2 steps (8 rows) ahead of the MFMAs, row indices 3
 constexpr int kTnrPf = 2;
 
-template <int FA, int FB, class SA, class SB>
+template <int FA, int FB, class AL, class BL>
 __global__ __launch_bounds__(TNR_WAVES * 64, 2) void gemm_tnr_kernel(
-    SA sa, SB sb, float* __restrict__ slab, float* __restrict__ bslab, int Nout, int Kout, int R,
+    AL al, BL bl, float* __restrict__ slab, float* __restrict__ bslab, int Nout, int Kout, int R,
     int rows_per_split, int tiles_k, int want_bias) {
+  using SA = TnrSrc<AL>;
+  using SB = TnrSrc<BL>;
   constexpr int TM = 16 * FA, TK = 16 * FB;
   __shared__ __attribute__((aligned(16))) float red[2][64 * FA * FB * 4];  // two partial tiles
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -174,18 +180,18 @@ __global__ __launch_bounds__(TNR_WAVES * 64, 2) void gemm_tnr_kernel(
   bool ok[NB], okn[NB];
   auto fetch_idx = [&](int t, int buf) {
     er[buf] = row_of(t, okn[buf]);
-    ia[buf] = sa.idx(er[buf]);
-    ib[buf] = sb.idx(er[buf]);
+    ia[buf] = SA::idx(al, er[buf]);
+    ib[buf] = SB::idx(bl, er[buf]);
   };
   auto fetch = [&](int buf) {  // data of the step whose indices sit in idx buffer buf
     ok[buf] = okn[buf];
-    sa.template fetch<FA>(er[buf], ia[buf], na, ra[buf]);
-    sb.template fetch<FB>(er[buf], ib[buf], kb, rb[buf]);
+    SA::template fetch<FA>(al, er[buf], ia[buf], na, ra[buf]);
+    SB::template fetch<FB>(bl, er[buf], ib[buf], kb, rb[buf]);
   };
   auto compute = [&](int buf) {
     float av[FA], bv[FB];
-    sa.template combine<FA>(ra[buf], av);
-    sb.template combine<FB>(rb[buf], bv);
+    SA::template combine<FA>(al, ra[buf], av);
+    SB::template combine<FB>(bl, rb[buf], bv);
 #pragma unroll
     for (int i = 0; i < FA; ++i) av[i] = ok[buf] ? av[i] : 0.f;  // rows past the split: 0
 #pragma unroll
@@ -302,21 +308,13 @@ __global__ __launch_bounds__(TNR_WAVES * 64, 2) void gemm_tnr_kernel(
   }
 }
 
-// splits: floor(target / tiles) workgroups (no CU gets an extra one), >= 16 rows per wave step set
+// >= 64 rows (4 steps per wave) per split, splits start on 16-row boundaries
 template <int FA, int FB>
-inline TnrPlan plan_tnr(int Nout, int Kout, int R, int target_wgs) {
-  TnrPlan p;
+inline TnPlan plan_tnr(int Nout, int Kout, int R, int target_wgs) {
+  TnPlan p;
   p.tiles_n = (Nout + 16 * FA - 1) / (16 * FA);
   p.tiles_k = (Kout + 16 * FB - 1) / (16 * FB);
-  const int tiles = p.tiles_n * p.tiles_k;
-  int splits = target_wgs / tiles;
-  const int max_splits = (R + 63) / 64;  // >= 64 rows (4 steps per wave) per split
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int rps = (R + splits - 1) / splits;
-  rps = (rps + 15) / 16 * 16;
-  p.splits = R > 0 ? (R + rps - 1) / rps : 1;
-  p.rows_per_split = rps;
+  tn_split(p, R, p.tiles_n * p.tiles_k, target_wgs, 64, 16);
   return p;
 }
 
@@ -325,12 +323,12 @@ template <int FA, int FB>
 inline bool tnr_ok(int Nout, int Kout) {
   return Nout >= FA && Kout >= FB && Nout % FA == 0 && Kout % FB == 0;
 }
-template <int FA, int FB, class SA, class SB>
-inline hipError_t launch_gemm_tnr(const SA& sa, const SB& sb, const TnrPlan& p, float* slab,
+template <int FA, int FB, class AL, class BL>
+inline hipError_t launch_gemm_tnr(const AL& al, const BL& bl, const TnPlan& p, float* slab,
                                   float* bslab, int Nout, int Kout, int R, bool want_bias,
                                   hipStream_t st) {
-  hipLaunchKernelGGL((gemm_tnr_kernel<FA, FB, SA, SB>), dim3(p.tiles_n * p.tiles_k * p.splits),
-                     dim3(TNR_WAVES * 64), 0, st, sa, sb, slab, bslab, Nout, Kout, R,
+  hipLaunchKernelGGL((gemm_tnr_kernel<FA, FB, AL, BL>), dim3(p.tiles_n * p.tiles_k * p.splits),
+                     dim3(TNR_WAVES * 64), 0, st, al, bl, slab, bslab, Nout, Kout, R,
                      p.rows_per_split, p.tiles_k, want_bias ? 1 : 0);
   return hipGetLastError();
 }

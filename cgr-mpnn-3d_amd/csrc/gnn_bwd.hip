@@ -142,7 +142,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   // complete then.  Node: caller's stream, slab2, reduced at once (flat after a split-bf16 TN:
   // this one ends the backward's main chain).
   auto wgrad = [&](auto site, const WgChoice& c, const void* img, const float* a, int vec,
-                   auto&& make_b, const auto& tnr_b, const WgDst& o, int bucket,
+                   auto&& make_b, const WgDst& o, int bucket,
                    int max_blocks = kReduceMaxBlocks) -> int {
     constexpr WgSite S = decltype(site)::value;
     constexpr bool own = S == WgSite::Node;
@@ -155,8 +155,8 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
               "cgr: a weight-gradient plan exceeds the split-K slabs the workspace was sized for");
     {
       ProfScope _p(wgrad_class(S, c.family), ws_st);
-      HIP_RET((wgrad_launch<S>(c, img, a, Hp, vec, make_b, tnr_b, sl, bsl, o.bias != nullptr,
-                               ws_st, b3 && !own ? pend.job : RedJob{})));
+      HIP_RET((wgrad_launch<S>(c, img, a, Hp, vec, make_b, sl, bsl, o.bias != nullptr, ws_st,
+                               b3 && !own ? pend.job : RedJob{})));
     }
     if (own) {
       ProfScope _p("splitk_reduce", st);
@@ -188,7 +188,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
 
   // side: dwf, dbf; dzn; dW_n = dzn^T [x | s], db_n (forked before the main stream's readout NT:
   // deferring it behind a layer, or enqueuing the NT first, A/B -4..-14 %).  dzn is materialised
-  // for the weight gradient only: the main stream's NT forms it inside the GEMM (LdActGrad).
+  // for the weight gradient only: the main stream's NT forms it inside the GEMM (LdActGradT).
   // the split-bf16 e-image TN takes dzn as the e-image the dzn kernel writes (dzn itself is
   // then never stored); the fp32 families read dzn
   const WgChoice ro = wgrad_pick(WgSite::Readout, d, x_aligned);
@@ -212,7 +212,6 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
                  [&](auto V) {
                    return LdConcat<decltype(V)::value>{xb, ldx, fv.a[D], Hp, Fx};
                  },
-                 TnrConcat{xb, ldx, fv.a[D], Hp, Fx},
                  WgDst{grads[CGR_PARAM_E2N_W(D)], F + H, 0, grads[CGR_PARAM_E2N_B(D)], F, Fx - F},
                  0);
   };
@@ -370,7 +369,6 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
                            [&](auto) {
                              return LdGatherDiff<false>{fv.a[l], fv.h[l], iv.src_s, iv.rev_s, Hp};
                            },
-                           TnrDiff{fv.a[l], fv.h[l], iv.src_s, iv.rev_s, Hp},
                            WgDst{grads[CGR_PARAM_CONV_W(l)], H, 0, grads[CGR_PARAM_CONV_B(l)]},
                            D - l);
       if (rc) return rc;
@@ -389,8 +387,8 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
       // at the join below), the last on the side stream: by then the main chain has ended (r05
       // trace: 13.5 us on 256 blocks for 1,300 logical ones, the step's tail), so it takes the GPU
       return wgrad(WgAt<WgSite::Edge>{}, wgrad_pick(WgSite::Edge, d, true), nullptr, dpre0, 4,
-                   [&](auto) { return LdPlain<4>{fv.e_s, d.Fep}; }, TnrRows{},
-                   WgDst{gW0, F + Fe, F, gb0}, -1, 1 << 20);
+                   [&](auto) { return LdPlain<4>{fv.e_s, d.Fep}; }, WgDst{gW0, F + Fe, F, gb0}, -1,
+                   1 << 20);
     }
     return flush();
   };
@@ -412,7 +410,6 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     // db0 comes from the edge-feature TN when there is one
     const int rc = wgrad(WgAt<WgSite::Node>{}, nd, img_main, Gs, vec_for(xb, ldx, F),
                          [&](auto V) { return LdPlain<decltype(V)::value>{xb, ldx}; },
-                         TnrRows{xb, ldx},
                          WgDst{gW0, F + Fe, 0, Fe > 0 ? nullptr : gb0, F, nd.Kout - F}, -1);
     if (rc) return rc;
   } else if (Fe == 0) {

@@ -176,7 +176,7 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
       HIP_RET(b3_pack_add(pm, b3_job(params[CGR_PARAM_CONV_W(l)], H, 1, H, H, fv.b3lf[l], lcols),
                           st));
     if (!mode.eval && (training & CGR_TRAIN_FOR_BACKWARD)) {  // the backward NT GEMMs' W^T images
-      B3PackJob rob = b3_job(Wn + F, 1, F + H, H, H, fv.b3rob, rcols);  // scaled by wf: LdActGrad
+      B3PackJob rob = b3_job(Wn + F, 1, F + H, H, H, fv.b3rob, rcols);  // scaled by wf: LdActGradT
       // (max pooling: the readout backward NT reads the materialised dzn, wf already in it)
       if (d.pool != CGR_POOL_MAX) rob.kscale = params[CGR_PARAM_FFN_W(D)];
       HIP_RET(b3_pack_add(pm, rob, st));

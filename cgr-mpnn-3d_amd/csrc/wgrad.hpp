@@ -41,8 +41,8 @@ using WgAt = std::integral_constant<WgSite, S>;  // a site as a compile-time arg
 // (gemm.hpp): the order of preference at every site
 enum class WgFamily { B3, Tnr, F32 };
 
-// One family at one site.  `plan`: the family's own plan in the terms of the slab layout all three
-// share ([splits][Nout][round_up(Kout, 4)], bias [splits][Nout]); converted in this file only.
+// One family at one site.  `plan`: what the family's planner returned -- all three plan in TnPlan
+// (gemm.hpp) and write the slab layout [splits][Nout][round_up(Kout, 4)], bias [splits][Nout].
 struct WgChoice {
   WgFamily family;
   int target;  // workgroups the plan aims at
@@ -74,18 +74,15 @@ inline hipError_t wg_f32_launch(const WgChoice& c, const AL& al, const BL& bl, f
 // register-direct fp32 TN: Nout % FA == 0 and Kout % FB == 0 (tnr_ok)
 template <int FA, int FB>
 inline WgChoice wg_tnr(int Nout, int Kout, int R, int target, bool x_side) {
-  const TnrPlan q = plan_tnr<FA, FB>(Nout, Kout, R, target);
   return WgChoice{WgFamily::Tnr, target, FA, FB, Nout, Kout, R,
-                  TnPlan{q.tiles_n, q.tiles_k, q.splits, q.rows_per_split},
-                  tnr_ok<FA, FB>(Nout, Kout), x_side};
+                  plan_tnr<FA, FB>(Nout, Kout, R, target), tnr_ok<FA, FB>(Nout, Kout), x_side};
 }
 // split-bf16 e-image TN: Nout up to 32 fragments and B extents inside 32-bit element offsets
 // (b3tni_ok; bl carries the B operand's leading dimensions, its pointers are not read)
 template <class BL>
 inline WgChoice wg_b3(const BL& bl, int Nout, int Kout, int R, int target, bool x_side) {
-  const B3TnPlan q = b3tn_plan(Nout, Kout, R, target);
   return WgChoice{WgFamily::B3, target, 0, 0, Nout, Kout, R,
-                  TnPlan{1, q.tiles_k, q.splits, q.rows_per_split}, b3tni_ok(bl, Nout, R), x_side};
+                  b3tn_plan(Nout, Kout, R, target), b3tni_ok(bl, Nout, R), x_side};
 }
 
 struct WgCandidates {
@@ -147,31 +144,29 @@ inline WgChoice wgrad_pick(WgSite s, const Dims& d, bool x_aligned) {
 }
 
 // Launch the picked family.  A [R, lda] fp32 (img: its e-image, which the split-bf16 family reads
-// instead), B as make_b(IC<V>) for the loader families (V = vec on the fp32 one, 4 on the
-// split-bf16 one) and as the tnr operand sb.  A site instantiates only the kernels it can pick.
-template <WgSite S, class MakeB, class SB>
+// instead), B as the loader make_b(IC<V>) returns: V = vec on the LDS-staged family, 4 on the
+// other two (16-byte rows: needs_aligned_x).  A site instantiates only the kernels it can pick.
+template <WgSite S, class MakeB>
 inline hipError_t wgrad_launch(const WgChoice& c, const void* img, const float* a, int64_t lda,
-                               int vec, MakeB&& make_b, const SB& sb, float* slab, float* bslab,
-                               bool want_bias, hipStream_t st, const RedJob& prev = RedJob{}) {
+                               int vec, MakeB&& make_b, float* slab, float* bslab, bool want_bias,
+                               hipStream_t st, const RedJob& prev = RedJob{}) {
   const TnPlan& p = c.plan;
+  const LdPlain<4> al{a, lda};
   if (c.family == WgFamily::F32)
     return with_vec(vec, [&](auto V) {
-      return wg_f32_launch(c, LdPlain<4>{a, lda}, make_b(V), slab, bslab, want_bias, st);
+      return wg_f32_launch(c, al, make_b(V), slab, bslab, want_bias, st);
     });
   if constexpr (S != WgSite::Edge) {
+    const auto bl = make_b(IC<4>{});
     if (c.family == WgFamily::B3)
-      return launch_b3tni(B3EImg{static_cast<const b3_u4*>(img), b3_eimg_cols(c.Nout)},
-                          make_b(IC<4>{}),
-                          B3TnPlan{p.tiles_k, p.splits, p.rows_per_split, (c.Nout + 15) / 16}, slab,
-                          bslab, c.Nout, c.Kout, c.R, want_bias, st, prev);
-    const TnrPlan q{p.tiles_n, p.tiles_k, p.splits, p.rows_per_split};
-    const TnrRows sa{a, lda};
+      return launch_b3tni(B3EImg{static_cast<const b3_u4*>(img), b3_eimg_cols(c.Nout)}, bl, p,
+                          slab, bslab, c.Nout, c.Kout, c.R, want_bias, st, prev);
     if constexpr (S == WgSite::Layer) {
       if (c.fa == 5)
-        return launch_gemm_tnr<5, 5>(sa, sb, q, slab, bslab, c.Nout, c.Kout, c.R, want_bias, st);
-      return launch_gemm_tnr<4, 4>(sa, sb, q, slab, bslab, c.Nout, c.Kout, c.R, want_bias, st);
+        return launch_gemm_tnr<5, 5>(al, bl, p, slab, bslab, c.Nout, c.Kout, c.R, want_bias, st);
+      return launch_gemm_tnr<4, 4>(al, bl, p, slab, bslab, c.Nout, c.Kout, c.R, want_bias, st);
     } else {
-      return launch_gemm_tnr<5, 4>(sa, sb, q, slab, bslab, c.Nout, c.Kout, c.R, want_bias, st);
+      return launch_gemm_tnr<5, 4>(al, bl, p, slab, bslab, c.Nout, c.Kout, c.R, want_bias, st);
     }
   }
   return hipErrorInvalidValue;

@@ -76,7 +76,7 @@ int main(int argc, char** argv) {
     LdGatherDiff<false> gd{a, h, dsrc + r0, drev + r0, Hp};
     EpLayer ep{bias, nullptr, h0 + (size_t)r0 * Hp, out + (size_t)r0 * Hp, nullptr, Hp, rows, H,
                ACT_RELU, 0u, 1.f, nullptr, 0};
-    CK((launch_gemm_nt<4, 1, 5, 1, decltype(gd), decltype(wl), EpLayer, 2>(gd, wl, ep, rows, H,
+    CK((launch_gemm_nt<4, 1, 5, 1, decltype(gd), decltype(wl), EpLayer>(gd, wl, ep, rows, H,
                                                                           H, s)));
   };
   auto tn = [&](hipStream_t s) {

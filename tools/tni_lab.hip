@@ -82,7 +82,7 @@ static void check(int R, int Nout, int Kout, bool gather, hipStream_t st) {
   }
   float *dA = todev(A), *dB = todev(Bp), *da = todev(a), *dh = todev(h);
   int *dsrc = todev(src), *drev = todev(rev);
-  const B3TnPlan p = b3tn_plan(Nout, Kout, R);
+  const TnPlan p = b3tn_plan(Nout, Kout, R);
   float *slab, *bslab, *out, *bias;
   b3_u4* img;
   CK(hipMalloc(&img, b3_eimg_bytes(R, Nout)));
@@ -159,7 +159,7 @@ int main(int argc, char** argv) {
   const int target = argc > 1 ? atoi(argv[1]) : kB3TnTarget;
   float t = time_us([&] { CK(b3_eimage(ddp, Hp, E, H, img, st)); }, st);
   printf("eimage E=%d H=%d: %.1f us (%.2f TB/s of 8 B/elem)\n", E, H, t, 8.0 * E * H / t * 1e-6);
-  const B3TnPlan p = b3tn_plan(H, H, E, target);
+  const TnPlan p = b3tn_plan(H, H, E, target);
   LdGatherDiff<false> bl{da, dh, dsrc, drev, Hp};
   const B3EImg ai{img, b3_eimg_cols(H)};
   t = time_us([&] { CK(launch_b3tni(ai, bl, p, slab, bslab, H, H, E, true, st)); }, st);
@@ -167,7 +167,7 @@ int main(int argc, char** argv) {
   printf("tni layer wgrad E=%d target=%d splits=%d wgs=%d: %.1f us (%.1f TFLOP/s fp32-equiv) + reduce %.1f us\n",
          E, target, p.splits, p.splits * p.tiles_k, t, fl / t * 1e-6, tr);
   CK(b3_eimage(dGs, Hp, Nn, H, imgn, st));
-  const B3TnPlan pn = b3tn_plan(H, F, Nn, 256);
+  const TnPlan pn = b3tn_plan(H, F, Nn, 256);
   LdPlain<4> bln{dx, F};
   const B3EImg an{imgn, b3_eimg_cols(H)};
   t = time_us([&] { CK(launch_b3tni(an, bln, pn, slab, bslab, H, F, Nn, false, st)); }, st);

@@ -92,7 +92,8 @@ int main() {
   CK(hipMalloc(&slab, (size_t)256 * H * Hp * 4));
   CK(hipMalloc(&bslab, (size_t)256 * H * 4));
 
-  // reference: LDS-staged TN (the library's layer weight-gradient configuration)
+  // one operand pair for both kernels; reference: LDS-staged TN (the library's layer
+  // weight-gradient configuration)
   LdPlain<4> al{dpre, Hp};
   LdGatherDiff<false> bl{a, h, dsrc, drev, Hp};
   const TnPlan p0 = plan_tn<5, 1, 5, 1>(H, H, E, 1024);
@@ -107,11 +108,9 @@ int main() {
   const double fl = 2.0 * E * H * H;
   printf("tn  (LDS, splits %3d)        %7.2f us  %6.1f TF/s\n", p0.splits, t0, fl / t0 * 1e-6);
 
-  TnrRows sa{dpre, Hp};
-  TnrDiff sb{a, h, dsrc, drev, Hp};
   for (int target : {256, 512, 768, 1024, 1536, 2048}) {
-    const TnrPlan p = plan_tnr<5, 5>(H, H, E, target);
-    auto run = [&] { CK((launch_gemm_tnr<5, 5>(sa, sb, p, slab, bslab, H, H, E, true, st))); };
+    const TnPlan p = plan_tnr<5, 5>(H, H, E, target);
+    auto run = [&] { CK((launch_gemm_tnr<5, 5>(al, bl, p, slab, bslab, H, H, E, true, st))); };
     CK(hipMemset(slab, 0, (size_t)p.splits * H * Hp * 4));
     run();
     CK(hipStreamSynchronize(st));

@@ -50,9 +50,9 @@ def classify(name: str, grid: int, grids_by_name: dict) -> str | None:
     if "k_b3_pack" in n:
         return "weight_pack"
     if "gemm_tnr_kernel" in n:  # register-direct fp32 TN (shapes the split-bf16 TN does not take)
-        if "TnrDiff" in n:
+        if "LdGatherDiff" in n:
             return "gemm_tn_wgrad_layer"
-        if "TnrConcat" in n:
+        if "LdConcat" in n:
             return "gemm_tn_wgrad_readout"
         return "gemm_tn_wgrad_node"
     if "gemm_tn_kernel" in n:  # fp32 fallback tiles (shapes the split-bf16 TN does not take)

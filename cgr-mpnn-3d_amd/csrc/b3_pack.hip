@@ -5,6 +5,7 @@
 
 #include "bwd_rows.hpp"
 #include "gemm_b3.hpp"
+#include "gemm_b3tn.hpp"
 
 namespace cgr {
 
@@ -112,7 +113,7 @@ hipError_t b3_pack(const B3PackJobs& jobs, hipStream_t st, const B3PackRiders* r
   return hipGetLastError();
 }
 
-// e-image of X [R, C] (gemm_b3.hpp, B3EImg): thread = (32-row step s, column c, 8-row chunk q),
+// e-image of X [R, C] (gemm_b3tn.hpp, B3EImg): thread = (32-row step s, column c, 8-row chunk q),
 // chunk fastest, so the four lanes of one column write its 64-byte slot of a plane whole and a
 // wave's stores cover 16 consecutive slots; its 8 loads (rows 32 s + 8 q + j, column c) run over
 // 16 consecutive columns of 4 rows per instruction.  Rows >= R and columns >= C are written as 0.

@@ -118,7 +118,7 @@ static void layout_prefix(const Dims& d, ArenaLayout& L, Bump& b) {
   L.cursor2 = L.cursor + 4 * N;
   L.graph_cnt = L.cursor2 + 4 * N;
   L.status = L.graph_cnt + 4 * B;
-  // + the ticket counters of the layer GEMMs' hub segments (EpLayerSeg: zero on entry, reset by
+  // + the ticket counters of the layer GEMMs' hub segments (EpLayerSeg, ep_fwd.hpp: zero on entry, reset by
   // each completer)
   L.fcnt = L.status + 16;
   // the layer forward runs in layer_cols(d), or in image_cols(d, H) over caller-packed images

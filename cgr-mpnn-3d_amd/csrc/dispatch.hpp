@@ -2,8 +2,9 @@
 //
 // GEMM families (one per shape class, picked per call site by same-box A/B of the whole step,
 // DESIGN.md §4):
-//   gemm_b3.hpp   split-bf16 NT (every NT GEMM of the model) and TN (layer / node / readout
-//                 weight gradients whose output rows fit one workgroup)
+//   gemm_b3.hpp   split-bf16 NT (every NT GEMM of the model)
+//   gemm_b3tn.hpp split-bf16 e-image TN (layer / node / readout weight gradients whose output
+//                 rows fit one workgroup)
 //   gemm_tnr.hpp  register-direct fp32 TN (weight gradients of shapes the split TN does not cover)
 //   gemm.hpp      LDS-staged fp32 NT / TN (standalone DMPNNConv, the edge-feature weight gradient
 //                 with K = Fe = 14, and any remaining shape)
@@ -19,6 +20,7 @@
 
 #include "gemm.hpp"
 #include "gemm_b3.hpp"
+#include "gemm_b3tn.hpp"
 #include "gemm_tnr.hpp"
 
 namespace cgr {

@@ -14,19 +14,13 @@
 // never reach memory.
 //
 // Segments crossing a row-tile boundary (at most one at each end of a tile) are completed inside
-// the launch by the LAST of their contributing workgroups (cdna_hip_programming.md §6
-// Guideline 16, counter form): each contributor hands over its partial sum -- a segment over two
-// row tiles adds it atomically to `dag` (two addends onto zero: order-independent), one over
-// three or more (a hub node: in-degree > rows per tile + 1) stores it write-through into a slot
-// fixed by the data (`part`, slot_of below), which the completer sums in row-tile order, so every
-// reduction is deterministic whatever the in-degree -- and
-// stores the segment's raw rows write-through (sc1), publishes them (vmcnt drain, barrier: no
-// release fence -- an agent-scope release writes back the XCD's L2, here full of the dpre rows
-// just stored: the fenced form ran each GEMM 15-20 us longer) and draws a ticket from the
-// segment's counter; the workgroup that draws the last ticket reads the partial sums and raw rows
-// with sc1 loads (no acquire) and applies the activation backward to all of the segment's rows,
-// then resets the counter and zeroes the segment's entries of the next layer's `dag` buffer (two
-// buffers alternate by layer).  No workgroup waits for another.
+// the launch by the LAST of their contributing workgroups (handoff.hpp: hand-over of the partial
+// sum into `dag` or a slot of `part`, ticket, fixed-order slot sum -- deterministic whatever the
+// in-degree).  Each contributor also stores the segment's raw rows write-through (sc1); the
+// workgroup that draws the last ticket reads the partial sums and raw rows with sc1 loads (no
+// acquire) and applies the activation backward to all of the segment's rows, then resets the
+// counter and zeroes the segment's entries of the next layer's `dag` buffer (two buffers
+// alternate by layer).  No workgroup waits for another.
 //
 // Unpaired edge lists (status bit 2) have no such locality: every workgroup stores its rows raw
 // and draws a ticket from this launch's own grid counter (one per fused launch, all zeroed by the
@@ -59,10 +53,8 @@ __host__ __device__ inline int unpaired_completers(int grid) {
   return k < 1 ? 1 : (k > 16 ? 16 : k);
 }
 
-
 template <bool EDGE_INIT>
 struct EpLayerBwdSeg {
-  static constexpr bool kSeg = false;
   static constexpr bool kTile = true;
   LayerBwdArgs a;      // the layer below (a.dpre written)
   float* raw;          // [M, Hp]: the raw rows of crossing segments (every row, unpaired)
@@ -93,18 +85,20 @@ struct EpLayerBwdSeg {
     return bwd_row_loads<EDGE_INIT>(a, rr, cc);
   }
 
-  // C: the tile's accumulators [BM][LDC] in LDS (column j of the tile = output column n0 + j);
-  // sd[q]: dst of rows m0 - 1 + q (q < BM + 2; distinct negative sentinels outside [0, M)),
-  // followed by 16 words of scratch; pass it takes piece q = tid + NT * it of the tile's BM x C4,
-  // row q / C4, column group q % C4; pv[it] holds pre4 of pass it's piece; tile_id: this
-  // workgroup's tile (tm * tiles_n + tn)
-  template <int BM, int BN, int NT, int LDC, int EIT>
-  __device__ __forceinline__ void tile(const Pre (&pv)[EIT], float* C, const int* sd, int m0,
-                                       int n0, int tile_id, int tid) const {
-    constexpr int C4 = BN / 4;
+  // t: B3NtTile (gemm_b3.hpp).  C: the tile's accumulators [BM][LDC] in LDS (column j of the tile
+  // = output column n0 + j); sd[q]: dst of row m0 - 1 + q; pass it takes piece q = tid + NT * it
+  // of the tile's BM x C4 (row q / C4, column group q % C4) with pv[it] = its pre4
+  template <class T>
+  __device__ __forceinline__ void tile(const T t) const {  // by value: see B3NtTile
+    using L = typename T::Lds;
+    constexpr int BM = T::BM, BN = T::BN, NT = T::NT, LDC = T::LDC, EIT = T::EIT, C4 = BN / 4;
+    const Pre (&pv)[EIT] = t.pv;
+    float* C = L::C(t.lds);
+    const int* sd = L::sd(t.lds);
+    int* done = L::done(t.lds);
+    const int m0 = t.m0, n0 = t.n0, tile_id = t.tile_id, tid = t.tid;
     const int nrow = min(BM, M - m0);
     const bool paired = (*status & 4) == 0;
-    int* scratch = const_cast<int*>(sd) + BM + 2;  // 16 words
     const int vh = sd[0] == sd[1] ? sd[0] : -3;               // head segment's node, if any
     const int vt = sd[nrow] == sd[nrow + 1] ? sd[nrow] : -3;  // tail segment's node, if any
     const uint64_t key = (!EDGE_INIT && a.thresh) ? *a.seed : 0;
@@ -115,9 +109,8 @@ struct EpLayerBwdSeg {
     // segment), dh = da - dm[rev(r)] -> the activation backward.  A segment crossing a row tile
     // (or every row, unpaired) stores its raw rows for the completer, and its first row in the
     // tile hands over the partial sum.  One loop per activation (the switch outside the loop).
-    const uint32_t* smask = reinterpret_cast<const uint32_t*>(sd + BM + 2 + 8);
-    const uint64_t mlo = smask[0] | ((uint64_t)smask[1] << 32);
-    const uint64_t mhi = smask[2] | ((uint64_t)smask[3] << 32);
+    uint64_t mlo, mhi;
+    L::load_mask(t.lds, mlo, mhi);
     CGR_STAMP(4);
     auto rows = [&](auto Ac) {
       constexpr int A = decltype(Ac)::value;
@@ -146,19 +139,9 @@ struct EpLayerBwdSeg {
           da = f4add(da, *reinterpret_cast<const float4*>(&C[k * LDC + 4 * c4]));
         if (head || tail) {
           sc1_store4(raw + i * a.Hp + col, x);
-          if (r == s) {
-            const int b = dst_ptr[v], ee = dst_ptr[v + 1];
-            if (seg_tiles(b, ee, BM) <= 2) {
-              float* g = dag + (int64_t)v * a.Hp + col;
-              atomicAdd(g, da.x);
-              atomicAdd(g + 1, da.y);
-              atomicAdd(g + 2, da.z);
-              atomicAdd(g + 3, da.w);
-            } else {
-              const int slot = slot_of(m0 / BM, b / BM);
-              sc1_store4(part + ((int64_t)tile_id * 2 + slot) * BN + 4 * c4, da);
-            }
-          }
+          if (r == s)
+            seg_hand_over<BM, BN>(dag + (int64_t)v * a.Hp + col, part, tile_id, m0 / BM, dst_ptr[v],
+                                  dst_ptr[v + 1], c4, da);
         } else {
           if (dscale) da = f4scale(da, dscale[v]);
           bwd_row_apply<EDGE_INIT, A>(a, i, col, f4sub(da, x), key, dsig, pv[it]);
@@ -184,33 +167,17 @@ struct EpLayerBwdSeg {
       ep_vm_drain();  // this wave's partial-sum atomics and raw-row stores
       __syncthreads();
       if (tid == 0) {
-        bool any = false;
         if (paired) {
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            const int v = k == 0 ? vh : (vt != vh ? vt : -3);
-            int done = 0;
-            if (v >= 0) {
-              const int contributors =
-                  (dst_ptr[v + 1] - 1) / BM - dst_ptr[v] / BM + 1;  // row tiles it touches
-              const int t = __hip_atomic_fetch_add(&cnt[(int64_t)v * tiles_n + tn], 1,
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              done = t == contributors - 1;
-            }
-            scratch[14 + k] = done ? v : -1;
-            any = any || done;
-          }
+          seg_tickets<BM>(vh, vt != vh ? vt : -3, dst_ptr, cnt, tiles_n, tn, done);
         } else {
           const int G = (int)gridDim.x, K = unpaired_completers(G);
-          const int t = __hip_atomic_fetch_add(gcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          any = t >= G - K;
-          scratch[14] = any ? t - (G - K) : -1;  // completer rank
-          scratch[15] = -1;
+          const int tk = __hip_atomic_fetch_add(gcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          done[0] = tk >= G - K ? tk - (G - K) : -1;  // completer rank
+          done[1] = -1;
         }
-        (void)any;
       }
       __syncthreads();
-      const int f0 = scratch[14], f1 = scratch[15];
+      const int f0 = done[0], f1 = done[1];
       scratch_f0 = f0;
       scratch_f1 = f1;
       if (paired) {
@@ -229,14 +196,8 @@ struct EpLayerBwdSeg {
           float4* das = reinterpret_cast<float4*>(C);
           __syncthreads();  // previous segment's das reads done
           for (int c4 = tid; c4 < C4; c4 += NT) {
-            float4 da = f4zero();
-            if (t1 - t0 + 1 <= 2) {
-              da = sc1_load4(dag + gv + n0 + 4 * c4);
-            } else {
-              for (int t = t0; t <= t1; ++t)
-                da = f4add(da, sc1_load4(part + ((int64_t)(t * tiles_n + tn) * 2 + slot_of(t, t0)) *
-                                                    BN + 4 * c4));
-            }
+            const float4 da = t1 - t0 + 1 <= 2 ? sc1_load4(dag + gv + n0 + 4 * c4)
+                                               : seg_slot_sum<BN>(part, t0, t1, tiles_n, tn, c4);
             das[c4] = dscale ? f4scale(da, dscale[v]) : da;
           }
           __syncthreads();
@@ -276,12 +237,12 @@ struct EpLayerBwdSeg {
           if (dev_err && f0 == 0)
             __hip_atomic_store(dev_err + kDevErrUnpairedSeen, 1, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_SYSTEM);
-          scratch[13] = late ? 1 : 0;
+          *L::late(t.lds) = late ? 1 : 0;
         }
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // loads stay below the wait
         // a completer that gave up waiting poisons what it writes (NaN), never a partial sum
-        const float poison = scratch[13] ? __builtin_nanf("") : 0.f;
+        const float poison = *L::late(t.lds) ? __builtin_nanf("") : 0.f;
         const int C4all = a.Hp >> 2;
         const int64_t mine = nodes > f0 ? (nodes - f0 + K - 1) / K : 0;
         float ds = 0.f;
@@ -308,11 +269,10 @@ struct EpLayerBwdSeg {
     // completer; zero when none starts there).  Unpaired: everything is the completer's, in its
     // own tile slot (all other slots are zero, so the sum is exact whatever the completer).
     if (!EDGE_INIT && a.dsig_part) {
-      static_assert(NT / 64 <= 8, "reduction scratch: words 0..7 after sd (B3NtShape)");
-      float* red = reinterpret_cast<float*>(scratch);
+      float* red = L::template red<NT>(t.lds);
       auto block_sum = [&](float x) {
         x = wave_sum(x);
-        __syncthreads();  // scratch free (flags read, previous sum consumed)
+        __syncthreads();  // red free (previous sum consumed)
         if ((tid & 63) == 0) red[tid >> 6] = x;
         __syncthreads();
         float s = 0.f;

@@ -8,7 +8,6 @@ namespace cgr {
 
 // C[r, c] = acc (+ bias[c])
 struct EpStore {
-  static constexpr bool kSeg = false;
   float* C;
   int64_t ld;
   int M, N;
@@ -48,7 +47,6 @@ struct EpStore {
 // gradient: sorted edge position r -> the caller's edge id perm[r]).  C is the caller's [M, N]
 // tensor (any N: scalar stores unless the row is float4-aligned).
 struct EpStorePermRows {
-  static constexpr bool kSeg = false;
   float* C;
   int64_t ld;
   int M, N;
@@ -77,7 +75,6 @@ struct EpStorePermRows {
 // gscale / nscale (nullable): mean pooling's per-graph 1 / count, mean aggregation's per-node
 // 1 / in-degree (ds feeds dh_D = ds[dst] / deg(dst) only)
 struct EpStoreRowScale {
-  static constexpr bool kSeg = false;
   float* C;
   int64_t ld;
   int M, N;
@@ -107,7 +104,6 @@ struct EpStoreRowScale {
 // D-MPNN layer (GNN.py:91-102):
 //   pre = (m W^T + b) + sigma * h0 ; h = dropout(act(pre))
 struct EpLayer {
-  static constexpr bool kSeg = false;
   const float* bias;
   const float* sigma;  // learnable skip weight (device scalar) or nullptr (= 1, GNN.py:97)
   const float* h0;
@@ -200,33 +196,9 @@ struct EpLayer {
   }
 };
 
-// EpLayer whose GEMM also produces the layer's scatter-add a[v] = sum_{dst(e) = v} h'[e]
-// (GNN.py:134) from its row tile (rows are dst-sorted; gemm_b3nt_kernel's SEG epilogue): the
-// "gather -> MLP -> segmented reduce" pass in one launch
-struct EpLayerSeg : EpLayer {
-  static constexpr bool kSeg = true;
-  const int* dst_s;  // [M] node of each (dst-sorted) row
-  float* aout;       // [nodes, lda]; crossing / empty segments zeroed beforehand
-  int64_t lda;
-  float* znext;      // or null: [nodes, lda] whose crossing segments this GEMM zeroes (eval ring)
-  // hub segments (over >= 3 row tiles: in-degree > rows per tile + 1), completed in fixed order
-  // by their last contributor (gemm_b3nt_kernel, handoff.hpp)
-  const int* dst_ptr;  // [nodes + 1] dst CSR of the sorted rows
-  float* part;         // [tiles, 2, BN] their partial sums (slot_of)
-  int* cnt;            // [nodes * tiles_n] tickets (zero on entry, left zero)
-  int tiles_n;
-  // apply4z that also returns the stored h (rows / columns outside: z unchanged)
-  template <int A = -1>
-  __device__ __forceinline__ float4 apply4z_h(int r, int c, float4 z, const Ctx& cx) const {
-    if (r >= M || c >= N) return z;
-    return this->template finish4<A>(r, c, z, cx);
-  }
-};
-
 // merged x-GEMM output [N, 2H]: columns [0, H) -> P (edge-init half), [H, 2H) -> Q (readout's
 // x-part); both internal [N, ld] buffers.
 struct EpSplit2 {
-  static constexpr bool kSeg = false;
   float* P;
   float* Q;
   int64_t ld;
@@ -269,7 +241,6 @@ struct EpSplit2 {
 
 // readout with the x-part precomputed: hn = act((s W_n[:, F:]^T + Q) + b_n)   (GNN.py:106-107)
 struct EpReadoutQ {
-  static constexpr bool kSeg = false;
   const float* bias;
   const float* Q;
   float* hn;

@@ -3,7 +3,7 @@
 //
 // Loaders (LdPlain, LdGatherRows, LdActGradT, LdGatherDiff, LdConcat) describe an operand once per
 // call site: this file's kernels call their row / fetch / combine, the split-bf16 GEMMs
-// (gemm_b3.hpp) and the register-direct TN (gemm_tnr.hpp) read the same structs through an
+// (gemm_b3.hpp, gemm_b3tn.hpp) and the register-direct TN (gemm_tnr.hpp) read the same structs through an
 // adapter beside their kernel (B3TnSrc<L>, TnrSrc<L>).
 //
 // The LDS-staged kernels run the standalone DMPNNConv, the narrow input-gradient GEMMs, the
@@ -447,7 +447,7 @@ inline hipError_t launch_gemm_nt(const AL& al, const BL& bl, const EP& ep, int M
 // TN split-K GEMM (weight gradients)
 // ------------------------------------------------------------------------------------------
 // The plan of a weight gradient on any of the three TN families (this file, gemm_tnr.hpp,
-// gemm_b3.hpp): tiles_n x tiles_k output tiles, each over `splits` ranges of rows_per_split rows;
+// gemm_b3tn.hpp): tiles_n x tiles_k output tiles, each over `splits` ranges of rows_per_split rows;
 // the grid is their product, the slabs are [splits][Nout][round_up(Kout, 4)] (bias [splits][Nout]).
 struct TnPlan {
   int tiles_n, tiles_k, splits, rows_per_split;

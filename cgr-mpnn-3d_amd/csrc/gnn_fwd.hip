@@ -12,6 +12,7 @@
 //          y   = (sum_{v in graph} hn[v]) . wf + bf                             (GNN.py:110)
 // The reference's discarded readout GEMM (GNN.py:105 -> lin(...) at :141) is not executed.
 #include "dispatch.hpp"
+#include "ep_fwd.hpp"
 #include "epilogues.hpp"
 #include "gnn_internal.hpp"
 #include "kernels.hpp"

@@ -129,7 +129,7 @@ struct WorkspaceLayout {
   // floats each slab / bias slab holds (slab, slab_b; slab2): the backward checks the plan it
   // picked against them before every weight-gradient launch
   size_t slab_elems = 0, bslab_elems = 0, slab2_elems = 0, bslab2_elems = 0;
-  // split-bf16 e-images (gemm_b3.hpp B3EImg) of the weight gradients' shared operand: dpre_l and
+  // split-bf16 e-images (gemm_b3tn.hpp B3EImg) of the weight gradients' shared operand: dpre_l and
   // dzn on the side stream (one at a time), Gs on the caller's stream; the top layer's dpre,
   // written by its activation kernel on the caller's stream (img_top)
   size_t img_side, img_main, img_top;

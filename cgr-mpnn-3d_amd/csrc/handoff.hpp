@@ -1,6 +1,8 @@
 // Workgroup-to-workgroup hand-off of the tile-crossing dst segments of the fused layer GEMMs
-// (gemm_b3.hpp EpLayerSeg, ep_bwd.hpp EpLayerBwdSeg): the last of a segment's contributing
-// workgroups completes it (cdna_hip_programming.md §6 Guideline 16, counter form).
+// (ep_fwd.hpp EpLayerSeg, ep_bwd.hpp EpLayerBwdSeg): the last of a segment's contributing
+// workgroups completes it (cdna_hip_programming.md §6 Guideline 16, counter form).  Both
+// epilogues are whole-tile functors of gemm_b3nt_kernel; `lds` below is its epilogue LDS block, laid
+// out by LDS = B3NtEpiLds (gemm_b3.hpp).
 #pragma once
 
 #include "common.hpp"
@@ -65,6 +67,53 @@ __device__ __forceinline__ float4 sc1_load4(const float* p) {
                      __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
                      __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
                      __hip_atomic_load(q + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+// ---- the three steps both segment epilogues take for a crossing segment ----
+// Hand-over of the partial sum `a` of segment [b, e) from row tile tm, column group c4: over two
+// row tiles it is added atomically to `sum` (its node's columns in a buffer zero on entry: two
+// addends onto zero, order-independent); over more, stored write-through into the data's slot.
+template <int BM, int BN>
+__device__ __forceinline__ void seg_hand_over(float* sum, float* part, int tile_id, int tm, int b,
+                                              int e, int c4, const float4& a) {
+  if (seg_tiles(b, e, BM) <= 2) {
+    atomicAdd(sum, a.x);
+    atomicAdd(sum + 1, a.y);
+    atomicAdd(sum + 2, a.z);
+    atomicAdd(sum + 3, a.w);
+  } else {
+    sc1_store4(part + ((int64_t)tile_id * 2 + slot_of(tm, b / BM)) * BN + 4 * c4, a);
+  }
+}
+// Ticket draw, by thread 0 alone, behind ep_vm_drain() + a barrier (every wave's hand-over has
+// left the CU: vmcnt counts stores.  No release fence -- an agent-scope release writes back the
+// XCD's L2, full of the rows just stored: the fenced form ran each GEMM 15-20 us longer): one
+// ticket from the counter of the head segment's node vh and of the tail's vt (< 0: none); the
+// workgroup drawing a segment's last ticket completes it: done[k] = its node, else -1.
+template <int BM>
+__device__ __forceinline__ void seg_tickets(int vh, int vt, const int* dst_ptr, int* cnt,
+                                            int tiles_n, int tn, int* done) {
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = k == 0 ? vh : vt;
+    int won = 0;
+    if (v >= 0) {
+      const int contributors = seg_tiles(dst_ptr[v], dst_ptr[v + 1], BM);
+      won = __hip_atomic_fetch_add(&cnt[(int64_t)v * tiles_n + tn], 1, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT) == contributors - 1;
+    }
+    done[k] = won ? v : -1;
+  }
+}
+// The completer's sum of a hub segment's slots, row tiles t0..t1 in order, column group c4 of
+// column tile tn: behind the wavefront acquire fence that keeps these loads below the ticket.
+template <int BN>
+__device__ __forceinline__ float4 seg_slot_sum(const float* part, int t0, int t1, int tiles_n,
+                                               int tn, int c4) {
+  float4 a = f4zero();
+  for (int t = t0; t <= t1; ++t)
+    a = f4add(a, sc1_load4(part + ((int64_t)(t * tiles_n + tn) * 2 + slot_of(t, t0)) * BN + 4 * c4));
+  return a;
 }
 
 }  // namespace cgr

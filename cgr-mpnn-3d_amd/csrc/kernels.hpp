@@ -30,7 +30,7 @@ hipError_t transpose_batch(const TransposeJobs& jobs, hipStream_t st);
 // h0 = act(P[src_s] + e_s @ W0e^T + b0) ; pre0 stored if non-null
 // edge init + a_0 = segsum_dst(h0) in one pass (Hp <= 512); hipErrorInvalidValue otherwise.
 // `zero` (may be null): the rows of a_1 .. a_n the layer GEMMs' segmented-sum epilogue
-// (EpLayerSeg, row tiles of tile_rows) does not store -- nodes without in-edges and nodes whose
+// (EpLayerSeg in ep_fwd.hpp, row tiles of tile_rows) does not store -- nodes without in-edges and nodes whose
 // in-edges cross a tile boundary (accumulated atomically) -- are zeroed here.
 struct SegZero {
   float* a[32];
@@ -67,7 +67,7 @@ hipError_t head_bwd(const float* dy, const float* g, const float* wf, int64_t B,
                     float* dg, float* dwf, float* dbf, hipStream_t st);
 
 // dzn[v] = dy[graph(v)] * wf * act'(zn[v])   (ReLU: hn > 0)
-// dzn (may be null: not materialised) and/or its e-image `img` (gemm_b3.hpp B3EImg; null: none)
+// dzn (may be null: not materialised) and/or its e-image `img` (gemm_b3tn.hpp B3EImg; null: none)
 // gscale (nullable): per-graph factor of dy (mean pooling: inv_cnt); pool_arg (nullable): max
 // pooling (pool_head_fwd's record): dzn[v, n] kept only where v is the column's first arg-max node
 // (entry >= 0) or, for an entry -count, where hn[v, n] equals the pooled g[graph(v), n], divided

@@ -1,6 +1,6 @@
 // Deterministic split-K slab reduction, one output item per thread: shared by the flat reduce
 // launch (kernels.hip) and the launch-boundary reduce in the split-bf16 TN's prologue
-// (gemm_b3.hpp), which folds the previous weight gradient's slabs into the next TN launch.
+// (gemm_b3tn.hpp), which folds the previous weight gradient's slabs into the next TN launch.
 #pragma once
 
 #include "common.hpp"

@@ -28,7 +28,7 @@ constexpr int kEdgeTnTargetWorkgroups = 256;
 constexpr int kTnrLayerTarget = 512;
 constexpr int kTnrNodeTarget = 512;
 constexpr int kTnrReadoutTarget = 256;
-// Split-bf16 TN (gemm_b3.hpp) workgroup targets (the layer's kB3TnTarget is beside its planner):
+// Split-bf16 TN (gemm_b3tn.hpp) workgroup targets (the layer's kB3TnTarget is beside its planner):
 // readout beside the critical readout NT 112 (A/B +0.7 % vs 176, 64 -6 %), node (the backward's
 // tail) 256 (+0.7 % vs 176, 352 -0.8 %)
 constexpr int kB3TnReadoutTarget = 112;
@@ -37,7 +37,7 @@ constexpr int kB3TnNodeTarget = 256;
 enum class WgSite { Readout, Layer, Node, Edge };
 template <WgSite S>
 using WgAt = std::integral_constant<WgSite, S>;  // a site as a compile-time argument
-// split-bf16 e-image TN (gemm_b3.hpp), register-direct fp32 TN (gemm_tnr.hpp), LDS-staged fp32 TN
+// split-bf16 e-image TN (gemm_b3tn.hpp), register-direct fp32 TN (gemm_tnr.hpp), LDS-staged fp32 TN
 // (gemm.hpp): the order of preference at every site
 enum class WgFamily { B3, Tnr, F32 };
 

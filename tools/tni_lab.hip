@@ -1,4 +1,4 @@
-// Lab for the e-image split-bf16 TN (csrc/gemm_b3.hpp gemm_b3tni_kernel): correctness against an
+// Lab for the e-image split-bf16 TN (csrc/gemm_b3tn.hpp gemm_b3tni_kernel): correctness against an
 // fp64 host reference and timing at the cfg2 shapes (layer, readout-like, node weight gradients).
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude tools/tni_lab.hip
 // (the round-3 ablation switches -DCGR_TNI_LAB=mask lived in the shipped header and were removed
@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "../cgr-mpnn-3d_amd/csrc/gemm.hpp"
-#include "../cgr-mpnn-3d_amd/csrc/gemm_b3.hpp"
+#include "../cgr-mpnn-3d_amd/csrc/gemm_b3tn.hpp"
 #include "../cgr-mpnn-3d_amd/csrc/b3_pack.hip"
 #include "../cgr-mpnn-3d_amd/csrc/kernels.hip"
 

@@ -26,7 +26,7 @@ from collections import defaultdict
 
 def classify(name: str, grid: int, grids_by_name: dict) -> str | None:
     n = name
-    if "gemm_b3tni_kernel" in n or "gemm_b3tn_kernel" in n:  # split-bf16 TN (gemm_b3.hpp)
+    if "gemm_b3tni_kernel" in n or "gemm_b3tn_kernel" in n:  # split-bf16 TN (gemm_b3tn.hpp)
         if "LdGatherDiff" in n:
             return "gemm_tn_wgrad_layer"
         if "LdConcat" in n:

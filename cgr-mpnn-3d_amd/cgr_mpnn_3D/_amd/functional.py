@@ -1,4 +1,5 @@
-"""autograd bridge: ``GNN.forward`` / backward -> ``cgr_gnn_forward`` / ``cgr_gnn_backward``.
+"""autograd bridge: ``GNN.forward`` / backward -> ``cgr_gnn_forward`` / ``cgr_gnn_backward``, and
+``GNN.encode`` (the model without its ffn head) -> ``cgr_gnn_encode`` / ``cgr_gnn_encode_backward``.
 
 The whole model step is ONE native call each way (≈25 kernel launches enqueued from C++), so the
 host cost per training step is two ctypes calls plus a few caching-allocator allocations; every
@@ -49,9 +50,10 @@ def _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, num_graphs):
 
 
 def _param_table(tensors):
+    """None -> NULL (the ffn slots of the headless calls, which the library never touches)."""
     arr = (c_void_p * len(tensors))()
     for i, t in enumerate(tensors):
-        arr[i] = t.data_ptr()
+        arr[i] = None if t is None else t.data_ptr()
     return arr
 
 
@@ -97,13 +99,14 @@ def _grad_views(params, depth):
     """(per-parameter (shape, stride, offset) of its view into the flat gradient buffer, buckets,
     total floats), memoised by the parameter shapes: grad_layout and the views' geometry are
     pure functions of them (the host cost of the eager backward, r06)."""
-    key = (depth,) + tuple(p.shape for p in params)
+    # (None: an absent ffn slot of the headless backward, no floats)
+    key = (depth,) + tuple((0,) if p is None else p.shape for p in params)
     hit = _GRAD_VIEWS.get(key)
     if hit is None:
         offs, buckets, total = grad_layout(key[1:], depth)
         geo = []
-        for o, p in zip(offs, params):
-            shape = tuple(p.shape)
+        for o, shape in zip(offs, key[1:]):
+            shape = tuple(shape)
             stride, acc = [], 1
             for d in reversed(shape):
                 stride.append(acc)
@@ -142,96 +145,139 @@ def read_status(arena, cfg, N, E, B) -> int:
     return int(arena[off:off + 4].view(torch.int32).item())
 
 
+def _function_forward(ctx, headless, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr,
+                      num_graphs, dropout_ps, seed, rng_counter, training, bucket_hook, params):
+    """forward of GNNFunction (cgr_gnn_forward -> y [B]) and, headless, of GNNEncodeFunction
+    (cgr_gnn_encode -> g [B, H]; the ffn slots of `params` are None)."""
+    lib = native.load()
+    cfg_tuple = resolve_config_tuple(cfg_tuple)  # the mode of this forward AND its backward
+    cfg = make_config(*cfg_tuple)
+    N, E, B = int(x.shape[0]), int(edge_index.shape[1]), int(num_graphs)
+    dev = x.device
+    arena_bytes = _memo_bytes(_ARENA_BYTES, lib.cgr_gnn_arena_bytes, cfg, cfg_tuple, N, E, B)
+    arena = torch.empty(arena_bytes, dtype=torch.uint8, device=dev)
+    y = torch.empty((B, cfg.hidden) if headless else B, dtype=torch.float32, device=dev)
+    bs = _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, B)
+    ptab = _param_table(params)
+    dps = _dropout_array(dropout_ps, cfg.depth)
+    # CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD (include/cgr_mpnn3d.h): the backward's
+    # weight-gradient operands are prepared only when a gradient is wanted (parameters, or
+    # x / edge_attr: the input gradients come after the parameter backward)
+    want_bwd = any(ctx.needs_input_grad[12:]) or ctx.needs_input_grad[1] or \
+        ctx.needs_input_grad[3]
+    flags = (native.TRAIN_DROPOUT if training else 0) | (
+        native.TRAIN_FOR_BACKWARD if want_bwd else 0)
+    if headless and want_bwd and (bucket_hook is not None or
+                                  _config.grad_bucket_hook is not None):
+        raise NotImplementedError(
+            "cgr_mpnn_3D: GNN.encode / a custom ffn head with a gradient-bucket hook: the "
+            "torch-side head's gradients are not in the flat bucket buffer the hook "
+            "all-reduces (data-parallel fingerprints are not supported)")
+    entry = lib.cgr_gnn_encode if headless else lib.cgr_gnn_forward
+    with native.device_guard(dev):
+        native.check(entry(ctypes.byref(cfg), ptab, ctypes.byref(bs), dps,
+                           ctypes.c_uint64(seed), native.ptr(rng_counter),
+                           flags, native.ptr(arena),
+                           native.ptr(y), native.stream_ptr(dev)))
+    if _config.strict:
+        raise_on_status(arena, cfg, N, E, B)
+    ctx.cfg_tuple = cfg_tuple
+    ctx.num_graphs = B
+    ctx.dropout_ps = dropout_ps
+    ctx.seed = seed
+    ctx.training = training
+    ctx.flags = flags
+    ctx.bucket_hook = bucket_hook
+    ctx.save_for_backward(x, edge_index, edge_attr, batch, graph_ptr, arena, *params)
+    return y
+
+
+def _function_backward(ctx, headless, dy):
+    """backward of GNNFunction (dy [B]) and, headless, of GNNEncodeFunction (dy = dg [B, H]: the
+    ffn slots of the returned gradients are None)."""
+    lib = native.load()
+    x, edge_index, edge_attr, batch, graph_ptr, arena, *params = ctx.saved_tensors
+    native.raise_device_errors(x.device, clear=False)  # an earlier backward's timeout
+    cfg = make_config(*ctx.cfg_tuple)
+    N, E, B = int(x.shape[0]), int(edge_index.shape[1]), ctx.num_graphs
+    dev = x.device
+    ws = torch.empty(_memo_bytes(_WS_BYTES, lib.cgr_gnn_workspace_bytes, cfg, ctx.cfg_tuple,
+                                 N, E, B), dtype=torch.uint8, device=dev)
+    # one flat gradient buffer in all-reduce bucket order, viewed per parameter
+    geo, buckets, total = _grad_views(params, cfg.depth)
+    flat = torch.empty(total, dtype=torch.float32, device=dev)
+    grads = [flat.as_strided(s, st, o) for s, st, o in geo]
+    dy = dy.contiguous().float()
+    bs = _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, B)
+    hook = ctx.bucket_hook if ctx.bucket_hook is not None else _config.grad_bucket_hook
+    # per-bucket ready events (recorded by the native backward) when the hook wants them
+    events = None
+    if hook is not None and hasattr(hook, "bucket_events"):
+        events = hook.bucket_events(dev, len(buckets))
+    evtab = None
+    if events is not None:
+        evtab = (c_void_p * len(events))(*[e.cuda_event for e in events])
+    if headless:
+        grads = [None if p is None else g for p, g in zip(params, grads)]
+    entry = lib.cgr_gnn_encode_backward if headless else lib.cgr_gnn_backward
+    with native.device_guard(dev):
+        native.check(entry(
+            ctypes.byref(cfg), _param_table(params), ctypes.byref(bs),
+            _dropout_array(ctx.dropout_ps, cfg.depth), ctypes.c_uint64(ctx.seed),
+            ctx.flags, native.ptr(arena), native.ptr(dy), _param_table(grads),
+            native.ptr(ws), evtab, native.stream_ptr(dev)))
+    dx = dea = None
+    if ctx.needs_input_grad[1] or ctx.needs_input_grad[3]:
+        # x.grad / edge_attr.grad (GNN.py:85-86,105-106): from what the backward left in `ws`
+        if ctx.needs_input_grad[1]:
+            dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
+        if ctx.needs_input_grad[3]:
+            dea = torch.empty(edge_attr.shape, dtype=torch.float32, device=dev)
+        entry = lib.cgr_gnn_encode_input_grads if headless else lib.cgr_gnn_input_grads
+        with native.device_guard(dev):
+            native.check(entry(
+                ctypes.byref(cfg), _param_table(params), ctypes.byref(bs), native.ptr(arena),
+                native.ptr(dy), native.ptr(ws),
+                native.ptr(dx) if dx is not None and dx.numel() else None,
+                native.ptr(dea) if dea is not None and dea.numel() else None,
+                native.stream_ptr(dev)))
+    if hook is not None:
+        # e.g. the RCCL all-reduce of every bucket, each started as soon as its event fires
+        # (cgr_mpnn_3D._amd.ddp); must leave the current stream ordered after its work
+        hook(flat, buckets, events)
+    return (None, dx, None, dea) + (None,) * 8 + tuple(grads)
+
+
 class GNNFunction(torch.autograd.Function):
     """y[B] = GNN(x, edge_index, edge_attr, batch; params) on the MI355X path."""
 
     @staticmethod
     def forward(ctx, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
                 dropout_ps, seed, rng_counter, training, bucket_hook, *params):
-        lib = native.load()
-        cfg_tuple = resolve_config_tuple(cfg_tuple)  # the mode of this forward AND its backward
-        cfg = make_config(*cfg_tuple)
-        N, E, B = int(x.shape[0]), int(edge_index.shape[1]), int(num_graphs)
-        dev = x.device
-        arena_bytes = _memo_bytes(_ARENA_BYTES, lib.cgr_gnn_arena_bytes, cfg, cfg_tuple, N, E, B)
-        arena = torch.empty(arena_bytes, dtype=torch.uint8, device=dev)
-        y = torch.empty(B, dtype=torch.float32, device=dev)
-        bs = _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, B)
-        ptab = _param_table(params)
-        dps = _dropout_array(dropout_ps, cfg.depth)
-        # CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD (include/cgr_mpnn3d.h): the backward's
-        # weight-gradient operands are prepared only when a gradient is wanted (parameters, or
-        # x / edge_attr: the input gradients come after the parameter backward)
-        want_bwd = any(ctx.needs_input_grad[12:]) or ctx.needs_input_grad[1] or \
-            ctx.needs_input_grad[3]
-        flags = (native.TRAIN_DROPOUT if training else 0) | (
-            native.TRAIN_FOR_BACKWARD if want_bwd else 0)
-        with native.device_guard(dev):
-            native.check(lib.cgr_gnn_forward(ctypes.byref(cfg), ptab, ctypes.byref(bs), dps,
-                                             ctypes.c_uint64(seed), native.ptr(rng_counter),
-                                             flags, native.ptr(arena),
-                                             native.ptr(y), native.stream_ptr(dev)))
-        if _config.strict:
-            raise_on_status(arena, cfg, N, E, B)
-        ctx.cfg_tuple = cfg_tuple
-        ctx.num_graphs = B
-        ctx.dropout_ps = dropout_ps
-        ctx.seed = seed
-        ctx.training = training
-        ctx.flags = flags
-        ctx.bucket_hook = bucket_hook
-        ctx.save_for_backward(x, edge_index, edge_attr, batch, graph_ptr, arena, *params)
-        return y
+        return _function_forward(ctx, False, cfg_tuple, x, edge_index, edge_attr, batch,
+                                 graph_ptr, num_graphs, dropout_ps, seed, rng_counter, training,
+                                 bucket_hook, params)
 
     @staticmethod
     def backward(ctx, dy):
-        lib = native.load()
-        x, edge_index, edge_attr, batch, graph_ptr, arena, *params = ctx.saved_tensors
-        native.raise_device_errors(x.device, clear=False)  # an earlier backward's timeout
-        cfg = make_config(*ctx.cfg_tuple)
-        N, E, B = int(x.shape[0]), int(edge_index.shape[1]), ctx.num_graphs
-        dev = x.device
-        ws = torch.empty(_memo_bytes(_WS_BYTES, lib.cgr_gnn_workspace_bytes, cfg, ctx.cfg_tuple,
-                                     N, E, B), dtype=torch.uint8, device=dev)
-        # one flat gradient buffer in all-reduce bucket order, viewed per parameter
-        geo, buckets, total = _grad_views(params, cfg.depth)
-        flat = torch.empty(total, dtype=torch.float32, device=dev)
-        grads = [flat.as_strided(s, st, o) for s, st, o in geo]
-        dy = dy.contiguous().float()
-        bs = _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, B)
-        hook = ctx.bucket_hook if ctx.bucket_hook is not None else _config.grad_bucket_hook
-        # per-bucket ready events (recorded by the native backward) when the hook wants them
-        events = None
-        if hook is not None and hasattr(hook, "bucket_events"):
-            events = hook.bucket_events(dev, len(buckets))
-        evtab = None
-        if events is not None:
-            evtab = (c_void_p * len(events))(*[e.cuda_event for e in events])
-        with native.device_guard(dev):
-            native.check(lib.cgr_gnn_backward(
-                ctypes.byref(cfg), _param_table(params), ctypes.byref(bs),
-                _dropout_array(ctx.dropout_ps, cfg.depth), ctypes.c_uint64(ctx.seed),
-                ctx.flags, native.ptr(arena), native.ptr(dy), _param_table(grads),
-                native.ptr(ws), evtab, native.stream_ptr(dev)))
-        dx = dea = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[3]:
-            # x.grad / edge_attr.grad (GNN.py:85-86,105-106): from what the backward left in `ws`
-            if ctx.needs_input_grad[1]:
-                dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
-            if ctx.needs_input_grad[3]:
-                dea = torch.empty(edge_attr.shape, dtype=torch.float32, device=dev)
-            with native.device_guard(dev):
-                native.check(lib.cgr_gnn_input_grads(
-                    ctypes.byref(cfg), _param_table(params), ctypes.byref(bs), native.ptr(arena),
-                    native.ptr(dy), native.ptr(ws),
-                    native.ptr(dx) if dx is not None and dx.numel() else None,
-                    native.ptr(dea) if dea is not None and dea.numel() else None,
-                    native.stream_ptr(dev)))
-        if hook is not None:
-            # e.g. the RCCL all-reduce of every bucket, each started as soon as its event fires
-            # (cgr_mpnn_3D._amd.ddp); must leave the current stream ordered after its work
-            hook(flat, buckets, events)
-        return (None, dx, None, dea) + (None,) * 8 + tuple(grads)
+        return _function_backward(ctx, False, dy)
+
+
+class GNNEncodeFunction(torch.autograd.Function):
+    """g[B, H] = pooling_fn(encoder(x, edge_index, edge_attr, batch; params)): the model without
+    its ffn head (cgr_gnn_encode / _encode_backward / _encode_input_grads).  `params` is the
+    C-ABI table with None in the two ffn slots; their gradients come back as None."""
+
+    @staticmethod
+    def forward(ctx, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
+                dropout_ps, seed, rng_counter, training, bucket_hook, *params):
+        return _function_forward(ctx, True, cfg_tuple, x, edge_index, edge_attr, batch,
+                                 graph_ptr, num_graphs, dropout_ps, seed, rng_counter, training,
+                                 bucket_hook, params)
+
+    @staticmethod
+    def backward(ctx, dg):
+        return _function_backward(ctx, True, dg)
 
 
 # predict arena sizes by (config, N, E, B): a pure function of its key (one ctypes call saved per
@@ -240,12 +286,13 @@ _PREDICT_ARENA_BYTES: dict = {}
 
 
 def gnn_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, dropout_ps,
-                seed, training, params, rng_counter=None):
+                seed, training, params, rng_counter=None, headless=False):
     """Forward-only GNN (cgr_gnn_predict): no saved activations.  What GNN.forward runs when no
     gradient is wanted (test.py:100-113 under torch.no_grad()).  The weight images are packed
     into the call's own arena by every call: no cache to go stale when an optimizer (FusedAdam,
     a replayed captured step) updates the parameters through raw pointers, and no buffer shared
-    with a predict still running on another stream."""
+    with a predict still running on another stream.  headless: cgr_gnn_encode_predict, the pooled
+    embedding g [B, H] (gnn_encode_predict)."""
     lib = native.load()
     cfg_tuple = resolve_config_tuple(cfg_tuple)
     cfg = make_config(*cfg_tuple)
@@ -261,10 +308,11 @@ def gnn_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graph
             _PREDICT_ARENA_BYTES.clear()
         _PREDICT_ARENA_BYTES[key] = nbytes
     arena = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    y = torch.empty(B, dtype=torch.float32, device=dev)
+    y = torch.empty((B, cfg.hidden) if headless else B, dtype=torch.float32, device=dev)
     bs = _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, B)
+    entry = lib.cgr_gnn_encode_predict if headless else lib.cgr_gnn_predict
     with native.device_guard(dev):
-        native.check(lib.cgr_gnn_predict(
+        native.check(entry(
             ctypes.byref(cfg), _param_table(params), ctypes.byref(bs),
             _dropout_array(dropout_ps, cfg.depth), ctypes.c_uint64(seed), native.ptr(rng_counter),
             native.TRAIN_DROPOUT if training else 0, None, native.ptr(arena),
@@ -292,3 +340,19 @@ def gnn_forward(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graph
     """rng_counter: optional device int64 tensor [1] the forward advances (graph-safe dropout)."""
     return GNNFunction.apply(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
                              dropout_ps, seed, rng_counter, training, bucket_hook, *params)
+
+
+def gnn_encode(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, dropout_ps,
+               seed, training, params, bucket_hook=None, rng_counter=None):
+    """The differentiable reaction fingerprint g [B, H] (GNNEncodeFunction); `params` in the
+    C-ABI table order with None in the ffn slots."""
+    return GNNEncodeFunction.apply(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr,
+                                   num_graphs, dropout_ps, seed, rng_counter, training,
+                                   bucket_hook, *params)
+
+
+def gnn_encode_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
+                       dropout_ps, seed, training, params, rng_counter=None):
+    """Forward-only fingerprint (cgr_gnn_encode_predict): gnn_predict without the head."""
+    return gnn_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
+                       dropout_ps, seed, training, params, rng_counter=rng_counter, headless=True)

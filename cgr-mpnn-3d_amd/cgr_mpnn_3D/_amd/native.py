@@ -96,6 +96,19 @@ SIGNATURES = [
     ("cgr_gnn_predict", c_int32,
      [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), POINTER(c_float), c_uint64,
       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the headless forms (added within ABI 9): g_out / dg [B, H] in place of y / dy [B]
+    ("cgr_gnn_encode", c_int32,
+     [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), POINTER(c_float), c_uint64,
+      c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("cgr_gnn_encode_backward", c_int32,
+     [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), POINTER(c_float), c_uint64,
+      c_int32, c_void_p, c_void_p, POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p]),
+    ("cgr_gnn_encode_input_grads", c_int32,
+     [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p]),
+    ("cgr_gnn_encode_predict", c_int32,
+     [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), POINTER(c_float), c_uint64,
+      c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("cgr_segment_sum", c_int32,
      [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     ("cgr_dmpnn_conv_scratch_bytes", c_int64, [c_int64, c_int64, c_int64]),

@@ -6,7 +6,9 @@ the reference (``cgr_mpnn_3D/models/GNN.py:8-145`` of tobjec/CGR-MPNN-3D), so ``
 given ``torch.manual_seed`` is identical (parameters are created in the reference's order).
 
 What differs is underneath: ``GNN.forward`` is one call into ``libcgr_mpnn3d.so`` (HIP kernels for
-gfx950) through ``cgr_mpnn_3D._amd.functional.GNNFunction``; the backward is one more call.  There
+gfx950) through ``cgr_mpnn_3D._amd.functional.GNNFunction``; the backward is one more call.
+``GNN.encode`` returns the pooled reaction fingerprint from the same kernels without the head,
+and a replaced ``ffn`` (any module) runs in PyTorch on top of it, as in the reference.  There
 is no CPU/PyTorch fallback: CPU tensors or a missing library raise.  ``torch_geometric`` is not
 required; PyG ``Batch``/``Data`` objects are accepted by duck typing (``x``, ``edge_index``,
 ``edge_attr``, ``batch`` and optionally ``ptr`` / ``num_graphs``).
@@ -32,7 +34,7 @@ import torch.nn.functional as F
 
 from .._amd import config as _config
 from .._amd import native
-from .._amd.functional import gnn_forward, gnn_predict
+from .._amd.functional import gnn_encode, gnn_encode_predict, gnn_forward, gnn_predict
 from .._amd.pool import (aggregation_code, global_add_pool, global_max_pool, global_mean_pool,
                          pooling_code)
 
@@ -99,7 +101,7 @@ def _warn_if_unpaired(edge_index):
         return False
     bad = (e[0, 1::2] != e[1, 0::2]) | (e[1, 1::2] != e[0, 0::2])
     if bool(bad.any()):
-        warnings.warn(_UNPAIRED_MSG, RuntimeWarning, stacklevel=3)
+        warnings.warn(_UNPAIRED_MSG, RuntimeWarning, stacklevel=4)
         return True
     return False
 
@@ -174,18 +176,22 @@ class GNN(nn.Module):
         return (s * 0x9E3779B97F4A7C15 + self._cgr_instance * 0xBF58476D1CE4E5B9) % 2**62
 
     # -- helpers -------------------------------------------------------------------------------
-    def native_parameters(self):
+    def native_parameters(self, head=True):
         """Parameters in the C-ABI table order (== reference state_dict order).  Read from the
         submodules' parameter dicts directly (what nn.Module.__getattr__ resolves to, without its
-        per-access lookups: this runs on every forward, r06 single-reaction latency)."""
+        per-access lookups: this runs on every forward, r06 single-reaction latency).
+        head=False (``encode``): None in the two ffn slots, whatever module ``ffn`` is."""
         mods = self._modules
-        ei, en, ff = (mods["edge_init"]._parameters, mods["edge_to_node"]._parameters,
-                      mods["ffn"]._parameters)
+        ei, en = mods["edge_init"]._parameters, mods["edge_to_node"]._parameters
         ps = [ei["weight"], ei["bias"]]
         for conv in mods["convs"]._modules.values():
             lp = conv._modules["lin"]._parameters
             ps += [lp["weight"], lp["bias"]]
-        ps += [en["weight"], en["bias"], ff["weight"], ff["bias"]]
+        if head:
+            ff = mods["ffn"]._parameters
+            ps += [en["weight"], en["bias"], ff["weight"], ff["bias"]]
+        else:
+            ps += [en["weight"], en["bias"], None, None]
         if self.use_learnable_skip:
             ps += list(mods["skip_weights"]._parameters.values())
         return ps
@@ -200,8 +206,19 @@ class GNN(nn.Module):
                 "(GNN.py:94-97) needs one uniform hidden size")
         return widths.pop()
 
+    def _fused_head(self) -> bool:
+        """Whether ``ffn`` is the reference's head, the one the fused kernels compute: exactly
+        ``nn.Linear(H, 1)`` with a bias."""
+        ff = self._modules["ffn"]
+        return type(ff) is nn.Linear and ff.out_features == 1 and \
+            ff._parameters["bias"] is not None and \
+            ff.in_features == self._modules["edge_to_node"].out_features
+
     # -- forward -------------------------------------------------------------------------------
-    def forward(self, data):
+    def _cgr_run(self, data, head):
+        """Input handling and checks shared by ``forward`` (head=True: the fused call, y [B]) and
+        ``encode`` (head=False: the headless call, g [B, H]), then the native call: its predict
+        form when no gradient is wanted."""
         x, edge_index, edge_attr, batch = data.x, data.edge_index, data.edge_attr, data.batch
         if not x.is_cuda:
             raise RuntimeError(
@@ -259,16 +276,18 @@ class GNN(nn.Module):
             import warnings
 
             self._cgr_unpaired_warned = True
-            warnings.warn(_UNPAIRED_MSG, RuntimeWarning, stacklevel=2)
+            warnings.warn(_UNPAIRED_MSG, RuntimeWarning, stacklevel=3)
         if not getattr(self, "_cgr_pairing_checked", False) and \
                 not torch.cuda.is_current_stream_capturing():
             self._cgr_pairing_checked = True
             if not getattr(self, "_cgr_unpaired_warned", False) and _warn_if_unpaired(edge_index):
                 self._cgr_unpaired_warned = True
 
-        params = self.native_parameters()
+        params = self.native_parameters(head)
         want_grad = x.requires_grad or edge_attr.requires_grad
         for i, p in enumerate(params):
+            if p is None:  # (encode: the ffn slots)
+                continue
             if p.dtype != torch.float32 or not p.is_cuda:
                 raise RuntimeError("cgr_mpnn_3D (MI355X): parameters must be fp32 CUDA tensors")
             if not p.is_contiguous():
@@ -287,10 +306,32 @@ class GNN(nn.Module):
             # no gradient wanted (test.py / the CLI run under torch.no_grad()): the forward-only
             # path, no saved activations
             # (no autograd here: the raw parameters' data pointers, no detach)
-            return gnn_predict(cfg, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, drop,
-                               seed, training, params, rng_counter=counter)
-        return gnn_forward(cfg, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, drop,
-                           seed, training, params, self._grad_bucket_hook, rng_counter=counter)
+            run = gnn_predict if head else gnn_encode_predict
+            return run(cfg, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, drop,
+                       seed, training, params, rng_counter=counter)
+        run = gnn_forward if head else gnn_encode
+        return run(cfg, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, drop,
+                   seed, training, params, self._grad_bucket_hook, rng_counter=counter)
+
+    def forward(self, data):
+        """``ffn(pooling_fn(h, batch)).squeeze(-1)`` (GNN.py:110).  With the reference's head --
+        ``type(self.ffn) is nn.Linear``, ``in_features == H``, ``out_features == 1``, a bias --
+        the whole model is one fused native call.  Any other ``ffn`` module (``nn.Linear(H, K)``
+        for K targets, an ``nn.Sequential`` MLP, a bias-free linear) runs in PyTorch on the native
+        fingerprint: ``self.ffn(self.encode(data)).squeeze(-1)``.  Forward hooks registered on
+        ``ffn`` do not change this routing (the fused call does not run the module, so they do
+        not fire for the default head): read the fingerprint with ``encode``."""
+        if self._fused_head():
+            return self._cgr_run(data, True)
+        return self.ffn(self._cgr_run(data, False)).squeeze(-1)
+
+    def encode(self, data):
+        """The learned reaction fingerprint ``pooling_fn(h, batch)`` [B, H] (the input of ``ffn``,
+        GNN.py:110), differentiable with respect to every encoder parameter, ``x`` and
+        ``edge_attr``.  Same input handling, dropout keying and counter advance as ``forward``;
+        under ``torch.no_grad()`` or when nothing requires grad, the forward-only form.  ``ffn``
+        takes no part, so it may be any module."""
+        return self._cgr_run(data, False)
 
 
 class DMPNNConv(nn.Module):

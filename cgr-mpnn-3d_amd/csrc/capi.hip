@@ -33,11 +33,21 @@ static std::unordered_map<const void*, int> g_arena_mode;
 // current generation (otherwise it silently returned garbage)
 static std::unordered_map<const void*, uint64_t> g_arena_gen;
 static std::unordered_map<const void*, std::pair<const void*, uint64_t>> g_ws_backward;
-static void note_forward(const void* arena, int flags, int mode = -1) {
+// ... and whether it was a headless forward (cgr_gnn_encode: no ffn head, the readout-backward
+// image unscaled for every pooling mode): the fused backward / input gradients refuse a headless
+// arena, the encode ones a fused arena
+static std::unordered_map<const void*, bool> g_arena_headless;
+static void note_forward(const void* arena, int flags, int mode = -1, bool headless = false) {
   std::lock_guard<std::mutex> lk(g_arena_mu);
   g_arena_flags[arena] = flags;
   g_arena_mode[arena] = mode;
+  g_arena_headless[arena] = headless;
   ++g_arena_gen[arena];
+}
+static bool forward_headless(const void* arena) {
+  std::lock_guard<std::mutex> lk(g_arena_mu);
+  const auto it = g_arena_headless.find(arena);
+  return it != g_arena_headless.end() && it->second;
 }
 static int forward_mode(const void* arena) {
   std::lock_guard<std::mutex> lk(g_arena_mu);
@@ -69,9 +79,10 @@ hipError_t pack_forward_images(const Dims& d, const float* const* params, const 
 int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch* b,
                       const float* dropout_p, uint64_t seed, int training, const void* arena,
                       const float* dy, float* const* grads, void* workspace,
-                      hipEvent_t const* bucket_events, hipStream_t st);
+                      hipEvent_t const* bucket_events, hipStream_t st, bool headless);
 int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* arena,
-                         const float* dy, void* workspace, float* dx, float* de, hipStream_t st);
+                         const float* dy, void* workspace, float* dx, float* de, hipStream_t st,
+                         bool headless);
 
 Dims make_dims(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B) {
   Dims d;
@@ -470,25 +481,101 @@ int cgr_graph_prep(const cgr_gnn_config* cfg, const cgr_batch* b, void* arena, v
   return cgr_graph_prep_impl(pa, (hipStream_t)stream);
 }
 
-int cgr_gnn_forward(const cgr_gnn_config* cfg, const float* const* params, const cgr_batch* b,
-                    const float* dropout_p, uint64_t seed, uint64_t* rng_counter,
-                    int32_t training, void* arena, float* y, void* stream) {
+// the ffn entries of a parameter / gradient table: NULL allowed in the headless (encode) calls
+static bool is_ffn_entry(const cgr_gnn_config* cfg, int i) {
+  return i == CGR_PARAM_FFN_W(cfg->depth) || i == CGR_PARAM_FFN_B(cfg->depth);
+}
+
+// cgr_gnn_forward (y [B]) / cgr_gnn_encode (headless: out = g_out [B, H])
+static int forward_entry(bool headless, const cgr_gnn_config* cfg, const float* const* params,
+                         const cgr_batch* b, const float* dropout_p, uint64_t seed,
+                         uint64_t* rng_counter, int32_t training, void* arena, float* out,
+                         void* stream) {
   clear_stale_hip_error();
   int rc = validate_config(cfg);
   if (rc) return rc;
   rc = validate_batch(cfg, b);
   if (rc) return rc;
-  CGR_CHECK(params != nullptr && arena != nullptr && y != nullptr,
-            "cgr: params / arena / y must not be NULL");
+  CGR_CHECK(params != nullptr && arena != nullptr && out != nullptr,
+            headless ? "cgr: params / arena / g_out must not be NULL"
+                     : "cgr: params / arena / y must not be NULL");
   CGR_CHECK((training & ~(CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)) == 0,
             "cgr: unknown `training` bits (CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)");
   const int np = cgr_gnn_num_params(cfg);
-  for (int i = 0; i < np; ++i) CGR_CHECK(params[i] != nullptr, "cgr: NULL parameter pointer");
+  for (int i = 0; i < np; ++i)
+    CGR_CHECK(params[i] != nullptr || (headless && is_ffn_entry(cfg, i)),
+              "cgr: NULL parameter pointer");
   const Dims d = make_dims(cfg, b->num_nodes, b->num_edges, b->num_graphs);
   note_forward(arena, -1);  // not usable by a backward unless the forward below succeeds
-  const int r = gnn_forward_impl(d, params, b, dropout_p, seed, rng_counter, training, arena, y,
-                                 (hipStream_t)stream, FwdMode{});
-  if (r == 0) note_forward(arena, training, cfg->precision);
+  FwdMode m;
+  m.headless = headless;
+  const int r = gnn_forward_impl(d, params, b, dropout_p, seed, rng_counter, training, arena, out,
+                                 (hipStream_t)stream, m);
+  if (r == 0) note_forward(arena, training, cfg->precision, headless);
+  return r;
+}
+
+int cgr_gnn_forward(const cgr_gnn_config* cfg, const float* const* params, const cgr_batch* b,
+                    const float* dropout_p, uint64_t seed, uint64_t* rng_counter,
+                    int32_t training, void* arena, float* y, void* stream) {
+  return forward_entry(false, cfg, params, b, dropout_p, seed, rng_counter, training, arena, y,
+                       stream);
+}
+
+int cgr_gnn_encode(const cgr_gnn_config* cfg, const float* const* params, const cgr_batch* b,
+                   const float* dropout_p, uint64_t seed, uint64_t* rng_counter, int32_t training,
+                   void* arena, float* g_out, void* stream) {
+  return forward_entry(true, cfg, params, b, dropout_p, seed, rng_counter, training, arena, g_out,
+                       stream);
+}
+
+// cgr_gnn_backward (up = dy [B]) / cgr_gnn_encode_backward (headless: up = dg [B, H])
+static int backward_entry(bool headless, const cgr_gnn_config* cfg, const float* const* params,
+                          const cgr_batch* b, const float* dropout_p, uint64_t seed,
+                          int32_t training, const void* arena, const float* up,
+                          float* const* grads, void* workspace, void* const* bucket_events,
+                          void* stream) {
+  const std::string fn = headless ? "cgr_gnn_encode_backward" : "cgr_gnn_backward";
+  const std::string fwd = headless ? "cgr_gnn_encode" : "cgr_gnn_forward";
+  clear_stale_hip_error();
+  int rc = validate_config(cfg);
+  if (rc) return rc;
+  rc = validate_batch(cfg, b);
+  if (rc) return rc;
+  CGR_CHECK(params != nullptr && arena != nullptr && up != nullptr && grads != nullptr &&
+                workspace != nullptr,
+            headless ? "cgr: params / arena / dg / grads / workspace must not be NULL"
+                     : "cgr: params / arena / dy / grads / workspace must not be NULL");
+  CGR_CHECK((training & ~(CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)) == 0,
+            "cgr: unknown `training` bits (CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)");
+  const int ff = forward_flags(arena);
+  CGR_CHECK(ff >= 0 && (ff & CGR_TRAIN_FOR_BACKWARD),
+            fn + ": `arena` was not filled by a successful " + fwd + " with "
+            "CGR_TRAIN_FOR_BACKWARD set");
+  CGR_CHECK(forward_headless(arena) == headless,
+            headless ? fn + ": `arena` was filled by cgr_gnn_forward (with the ffn head); its "
+                            "backward is cgr_gnn_backward"
+                     : fn + ": `arena` was filled by cgr_gnn_encode (headless, no ffn head); its "
+                            "backward is cgr_gnn_encode_backward");
+  CGR_CHECK((ff & CGR_TRAIN_DROPOUT) == (training & CGR_TRAIN_DROPOUT),
+            fn + ": `training` dropout bit differs from the forward's");
+  CGR_CHECK(forward_mode(arena) == cfg->precision,
+            fn + ": the config's precision differs from the mode `arena`'s forward "
+            "ran in");
+  const int np = cgr_gnn_num_params(cfg);
+  for (int i = 0; i < np; ++i) {
+    if (headless && is_ffn_entry(cfg, i)) continue;  // never read or written
+    CGR_CHECK(params[i] != nullptr, "cgr: NULL parameter pointer");
+    CGR_CHECK(grads[i] != nullptr, "cgr: NULL gradient pointer");
+  }
+  const Dims d = make_dims(cfg, b->num_nodes, b->num_edges, b->num_graphs);
+  if (bucket_events)
+    for (int i = 0; i < CGR_GRAD_BUCKETS(cfg->depth); ++i)
+      CGR_CHECK(bucket_events[i] != nullptr, fn + ": NULL bucket event");
+  const int r = gnn_backward_impl(d, params, b, dropout_p, seed, training, arena, up, grads,
+                                  workspace, reinterpret_cast<hipEvent_t const*>(bucket_events),
+                                  (hipStream_t)stream, headless);
+  if (r == 0) note_backward(arena, workspace);
   return r;
 }
 
@@ -496,68 +583,71 @@ int cgr_gnn_backward(const cgr_gnn_config* cfg, const float* const* params, cons
                      const float* dropout_p, uint64_t seed, int32_t training, const void* arena,
                      const float* dy, float* const* grads, void* workspace,
                      void* const* bucket_events, void* stream) {
+  return backward_entry(false, cfg, params, b, dropout_p, seed, training, arena, dy, grads,
+                        workspace, bucket_events, stream);
+}
+
+int cgr_gnn_encode_backward(const cgr_gnn_config* cfg, const float* const* params,
+                            const cgr_batch* b, const float* dropout_p, uint64_t seed,
+                            int32_t training, const void* arena, const float* dg,
+                            float* const* grads, void* workspace, void* const* bucket_events,
+                            void* stream) {
+  return backward_entry(true, cfg, params, b, dropout_p, seed, training, arena, dg, grads,
+                        workspace, bucket_events, stream);
+}
+
+// cgr_gnn_input_grads (up = dy [B]) / cgr_gnn_encode_input_grads (headless: up = dg [B, H])
+static int input_grads_entry(bool headless, const cgr_gnn_config* cfg,
+                             const float* const* params, const cgr_batch* b, const void* arena,
+                             const float* up, void* workspace, float* dx, float* dedge_attr,
+                             void* stream) {
+  const std::string fn = headless ? "cgr_gnn_encode_input_grads" : "cgr_gnn_input_grads";
+  const std::string fwd = headless ? "cgr_gnn_encode" : "cgr_gnn_forward";
+  const std::string bwd = headless ? "cgr_gnn_encode_backward" : "cgr_gnn_backward";
   clear_stale_hip_error();
   int rc = validate_config(cfg);
   if (rc) return rc;
   rc = validate_batch(cfg, b);
   if (rc) return rc;
-  CGR_CHECK(params != nullptr && arena != nullptr && dy != nullptr && grads != nullptr &&
-                workspace != nullptr,
-            "cgr: params / arena / dy / grads / workspace must not be NULL");
-  CGR_CHECK((training & ~(CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)) == 0,
-            "cgr: unknown `training` bits (CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)");
+  CGR_CHECK(params != nullptr && arena != nullptr && up != nullptr && workspace != nullptr,
+            headless ? "cgr: params / arena / dg / workspace must not be NULL"
+                     : "cgr: params / arena / dy / workspace must not be NULL");
   const int ff = forward_flags(arena);
   CGR_CHECK(ff >= 0 && (ff & CGR_TRAIN_FOR_BACKWARD),
-            "cgr_gnn_backward: `arena` was not filled by a successful cgr_gnn_forward with "
+            fn + ": `arena` was not filled by a successful " + fwd + " with "
             "CGR_TRAIN_FOR_BACKWARD set");
-  CGR_CHECK((ff & CGR_TRAIN_DROPOUT) == (training & CGR_TRAIN_DROPOUT),
-            "cgr_gnn_backward: `training` dropout bit differs from the forward's");
+  CGR_CHECK(forward_headless(arena) == headless,
+            headless ? fn + ": `arena` was filled by cgr_gnn_forward (with the ffn head); its "
+                            "input gradients are cgr_gnn_input_grads"
+                     : fn + ": `arena` was filled by cgr_gnn_encode (headless, no ffn head); its "
+                            "input gradients are cgr_gnn_encode_input_grads");
   CGR_CHECK(forward_mode(arena) == cfg->precision,
-            "cgr_gnn_backward: the config's precision differs from the mode `arena`'s forward "
+            fn + ": the config's precision differs from the mode `arena`'s forward "
             "ran in");
+  CGR_CHECK(backward_matches(arena, workspace),
+            fn + ": `workspace` does not hold a " + bwd + " of this `arena`'s "
+            "latest forward (run the backward first, with the same arena and workspace)");
+  CGR_CHECK(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dedge_attr & 15) == 0,
+            fn + ": dx / dedge_attr must be 16-byte aligned (or NULL)");
   const int np = cgr_gnn_num_params(cfg);
-  for (int i = 0; i < np; ++i) {
-    CGR_CHECK(params[i] != nullptr, "cgr: NULL parameter pointer");
-    CGR_CHECK(grads[i] != nullptr, "cgr: NULL gradient pointer");
-  }
+  for (int i = 0; i < np; ++i)
+    CGR_CHECK(params[i] != nullptr || (headless && is_ffn_entry(cfg, i)),
+              "cgr: NULL parameter pointer");
   const Dims d = make_dims(cfg, b->num_nodes, b->num_edges, b->num_graphs);
-  if (bucket_events)
-    for (int i = 0; i < CGR_GRAD_BUCKETS(cfg->depth); ++i)
-      CGR_CHECK(bucket_events[i] != nullptr, "cgr_gnn_backward: NULL bucket event");
-  const int r = gnn_backward_impl(d, params, b, dropout_p, seed, training, arena, dy, grads,
-                                  workspace, reinterpret_cast<hipEvent_t const*>(bucket_events),
-                                  (hipStream_t)stream);
-  if (r == 0) note_backward(arena, workspace);
-  return r;
+  return gnn_input_grads_impl(d, params, arena, up, workspace, dx, dedge_attr,
+                              (hipStream_t)stream, headless);
 }
 
 int cgr_gnn_input_grads(const cgr_gnn_config* cfg, const float* const* params,
                         const cgr_batch* b, const void* arena, const float* dy, void* workspace,
                         float* dx, float* dedge_attr, void* stream) {
-  clear_stale_hip_error();
-  int rc = validate_config(cfg);
-  if (rc) return rc;
-  rc = validate_batch(cfg, b);
-  if (rc) return rc;
-  CGR_CHECK(params != nullptr && arena != nullptr && dy != nullptr && workspace != nullptr,
-            "cgr: params / arena / dy / workspace must not be NULL");
-  const int ff = forward_flags(arena);
-  CGR_CHECK(ff >= 0 && (ff & CGR_TRAIN_FOR_BACKWARD),
-            "cgr_gnn_input_grads: `arena` was not filled by a successful cgr_gnn_forward with "
-            "CGR_TRAIN_FOR_BACKWARD set");
-  CGR_CHECK(forward_mode(arena) == cfg->precision,
-            "cgr_gnn_input_grads: the config's precision differs from the mode `arena`'s forward "
-            "ran in");
-  CGR_CHECK(backward_matches(arena, workspace),
-            "cgr_gnn_input_grads: `workspace` does not hold a cgr_gnn_backward of this `arena`'s "
-            "latest forward (run the backward first, with the same arena and workspace)");
-  CGR_CHECK(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dedge_attr & 15) == 0,
-            "cgr_gnn_input_grads: dx / dedge_attr must be 16-byte aligned (or NULL)");
-  const int np = cgr_gnn_num_params(cfg);
-  for (int i = 0; i < np; ++i) CGR_CHECK(params[i] != nullptr, "cgr: NULL parameter pointer");
-  const Dims d = make_dims(cfg, b->num_nodes, b->num_edges, b->num_graphs);
-  return gnn_input_grads_impl(d, params, arena, dy, workspace, dx, dedge_attr,
-                              (hipStream_t)stream);
+  return input_grads_entry(false, cfg, params, b, arena, dy, workspace, dx, dedge_attr, stream);
+}
+
+int cgr_gnn_encode_input_grads(const cgr_gnn_config* cfg, const float* const* params,
+                               const cgr_batch* b, const void* arena, const float* dg,
+                               void* workspace, float* dx, float* dedge_attr, void* stream) {
+  return input_grads_entry(true, cfg, params, b, arena, dg, workspace, dx, dedge_attr, stream);
 }
 
 int64_t cgr_gnn_image_bytes(const cgr_gnn_config* cfg) {
@@ -583,27 +673,49 @@ int64_t cgr_gnn_predict_arena_bytes(const cgr_gnn_config* cfg, int64_t N, int64_
   return (int64_t)eval_arena_layout(make_dims(cfg, N, E, B)).bytes;
 }
 
-int cgr_gnn_predict(const cgr_gnn_config* cfg, const float* const* params, const cgr_batch* b,
-                    const float* dropout_p, uint64_t seed, uint64_t* rng_counter,
-                    int32_t training, const void* images, void* arena, float* y, void* stream) {
+// cgr_gnn_predict (y [B]) / cgr_gnn_encode_predict (headless: out = g_out [B, H])
+static int predict_entry(bool headless, const cgr_gnn_config* cfg, const float* const* params,
+                         const cgr_batch* b, const float* dropout_p, uint64_t seed,
+                         uint64_t* rng_counter, int32_t training, const void* images,
+                         void* arena, float* out, void* stream) {
   clear_stale_hip_error();
   int rc = validate_config(cfg);
   if (rc) return rc;
   rc = validate_batch(cfg, b);
   if (rc) return rc;
-  CGR_CHECK(params != nullptr && arena != nullptr && y != nullptr,
-            "cgr: params / arena / y must not be NULL");
+  CGR_CHECK(params != nullptr && arena != nullptr && out != nullptr,
+            headless ? "cgr: params / arena / g_out must not be NULL"
+                     : "cgr: params / arena / y must not be NULL");
   CGR_CHECK((training & ~CGR_TRAIN_DROPOUT) == 0,
-            "cgr_gnn_predict: `training` may only hold CGR_TRAIN_DROPOUT (no backward follows)");
+            std::string(headless ? "cgr_gnn_encode_predict" : "cgr_gnn_predict") +
+                ": `training` may only hold CGR_TRAIN_DROPOUT (no backward follows)");
   const int np = cgr_gnn_num_params(cfg);
-  for (int i = 0; i < np; ++i) CGR_CHECK(params[i] != nullptr, "cgr: NULL parameter pointer");
+  for (int i = 0; i < np; ++i)
+    CGR_CHECK(params[i] != nullptr || (headless && is_ffn_entry(cfg, i)),
+              "cgr: NULL parameter pointer");
   const Dims d = make_dims(cfg, b->num_nodes, b->num_edges, b->num_graphs);
   FwdMode m;
   m.eval = true;
   m.images = images;
+  m.headless = headless;
   note_forward(arena, -1);  // never a backward's arena
-  return gnn_forward_impl(d, params, b, dropout_p, seed, rng_counter, training, arena, y,
+  return gnn_forward_impl(d, params, b, dropout_p, seed, rng_counter, training, arena, out,
                           (hipStream_t)stream, m);
+}
+
+int cgr_gnn_predict(const cgr_gnn_config* cfg, const float* const* params, const cgr_batch* b,
+                    const float* dropout_p, uint64_t seed, uint64_t* rng_counter,
+                    int32_t training, const void* images, void* arena, float* y, void* stream) {
+  return predict_entry(false, cfg, params, b, dropout_p, seed, rng_counter, training, images,
+                       arena, y, stream);
+}
+
+int cgr_gnn_encode_predict(const cgr_gnn_config* cfg, const float* const* params,
+                           const cgr_batch* b, const float* dropout_p, uint64_t seed,
+                           uint64_t* rng_counter, int32_t training, const void* images,
+                           void* arena, float* g_out, void* stream) {
+  return predict_entry(true, cfg, params, b, dropout_p, seed, rng_counter, training, images,
+                       arena, g_out, stream);
 }
 
 int32_t cgr_device_errors(int32_t device, int32_t clear) {

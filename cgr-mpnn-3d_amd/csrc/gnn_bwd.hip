@@ -69,7 +69,7 @@ struct PendingReduce {
 int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch* b,
                       const float* dropout_p, uint64_t seed, int training, const void* arena,
                       const float* dy, float* const* grads, void* workspace,
-                      hipEvent_t const* bucket_events, hipStream_t st) {
+                      hipEvent_t const* bucket_events, hipStream_t st, bool headless) {
   const ArenaLayout L = arena_layout(d);
   const IndexView iv = index_view(const_cast<void*>(arena), L);
   const FloatView fv = float_view(const_cast<void*>(arena), L, d);
@@ -194,13 +194,18 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   const WgChoice ro = wgrad_pick(WgSite::Readout, d, x_aligned);
   const bool ro_b3 = ro.family == WgFamily::B3;
   const bool max_pool = fv.pool_arg != nullptr;  // global_max_pool (CGR_POOL_MAX)
+  // headless (cgr_gnn_encode_backward): `dy` is dg [B, H], a general cotangent of the pooled
+  // embedding -- neither a row nor a column factor, so every pooling mode takes max pooling's
+  // route: dzn materialised on the main stream before the fork, the NT over the unscaled image;
+  // no head gradients (the ffn entries of params / grads are not touched)
+  const bool dzn_main = max_pool || headless;
   auto side_readout = [&]() -> int {
-    {  // dwf = dy^T g, dbf: off the main chain (step A/B +0.8 %)
+    if (!headless) {  // dwf = dy^T g, dbf: off the main chain (step A/B +0.8 %)
       ProfScope _p("head_bwd", side);
       HIP_RET(head_bwd(dy, fv.g, params[CGR_PARAM_FFN_W(D)], d.B, H, Hp, nullptr,
                        grads[CGR_PARAM_FFN_W(D)], grads[CGR_PARAM_FFN_B(D)], side));
     }
-    if (!max_pool) {  // (max pooling: dzn and its image came from the main stream, below)
+    if (!dzn_main) {  // (max pooling: dzn and its image came from the main stream, below)
       ProfScope _p("readout_act_bwd", side);
       HIP_RET(readout_act_bwd(dy, params[CGR_PARAM_FFN_W(D)], iv.node_graph, fv.hn, fv.zn, N, H,
                               Hp, d.act, ro_b3 ? nullptr : dzn, ro_b3 ? img_side : nullptr,
@@ -222,7 +227,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     ProfScope _p("gemm_nt_readout_bwd", st);
     const float* m = d.act == ACT_RELU ? fv.hn : fv.zn;
     const b3_u4* img = static_cast<const b3_u4*>(fv.b3rob);
-    if (max_pool) {  // ds = dzn W_n[:, F:] with dzn materialised (its per-element arg-max mask is
+    if (dzn_main) {  // ds = dzn W_n[:, F:] with dzn materialised (its per-element arg-max mask is
                      // no row / column factor); the image is unscaled (gnn_fwd.hip)
       const EpStoreRowScale ep{ds, Hp, N, H, nullptr, iv.node_graph, nullptr, fv.inv_deg};
       HIP_RET(launch_b3nt(LdPlain<4>{dzn, Hp}, img, readout_cols(d), ep, N, H, H, st, acc));
@@ -244,7 +249,11 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   // recorded before it, the side work after -- same dependencies) moves the NT onto the forward's
   // hardware queue in a captured graph but puts the first layer NT beside the readout TN: r05
   // same-box A/B 344.0k -> 341.0k reactions/s (3 runs each, profiles/r05_ro_first_ab.txt)
-  if (max_pool) {  // dzn (fp32 for the NT, and the TN's e-image) before the fork
+  if (headless) {
+    ProfScope _p("readout_act_bwd_dg", st);
+    HIP_RET(readout_act_bwd_dg(dy, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act, dzn,
+                               ro_b3 ? img_side : nullptr, st, fv.inv_cnt, fv.pool_arg, fv.g));
+  } else if (max_pool) {  // dzn (fp32 for the NT, and the TN's e-image) before the fork
     ProfScope _p("readout_act_bwd", st);
     HIP_RET(readout_act_bwd(dy, params[CGR_PARAM_FFN_W(D)], iv.node_graph, fv.hn, fv.zn, N, H, Hp,
                             d.act, dzn, ro_b3 ? img_side : nullptr, st, nullptr, fv.pool_arg, fv.g));
@@ -447,7 +456,8 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
 // in fp32 (the backward keeps them as e-images only) and the stacked weight slices transposed
 // into wxT, so both products are one fp32 MFMA NT launch each (gemm.hpp), exact-fp32 products.
 int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* arena,
-                         const float* dy, void* workspace, float* dx, float* de, hipStream_t st) {
+                         const float* dy, void* workspace, float* dx, float* de, hipStream_t st,
+                         bool headless) {
   const ArenaLayout L = arena_layout(d);
   const IndexView iv = index_view(const_cast<void*>(arena), L);
   const FloatView fv = float_view(const_cast<void*>(arena), L, d);
@@ -472,8 +482,12 @@ int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* 
     {
       ProfScope _p("input_grad_prep", st);
       HIP_RET(segment_sum(dpre0, Hp, iv.src_list, iv.src_ptr, N, H, Gs, Hp, st));
-      HIP_RET(readout_act_bwd(dy, params[CGR_PARAM_FFN_W(D)], iv.node_graph, fv.hn, fv.zn, N, H,
-                              Hp, d.act, dzn, nullptr, st, fv.inv_cnt, fv.pool_arg, fv.g));
+      if (headless)  // `dy` is dg [B, H] (cgr_gnn_encode_input_grads)
+        HIP_RET(readout_act_bwd_dg(dy, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act, dzn, nullptr,
+                                   st, fv.inv_cnt, fv.pool_arg, fv.g));
+      else
+        HIP_RET(readout_act_bwd(dy, params[CGR_PARAM_FFN_W(D)], iv.node_graph, fv.hn, fv.zn, N, H,
+                                Hp, d.act, dzn, nullptr, st, fv.inv_cnt, fv.pool_arg, fv.g));
       TransposeJobs tj{};  // wxT [F, ldw] = [W0[:, :F]^T | W_n[:, :F]^T]
       tj.job[0] = TransposeJob{params[CGR_PARAM_EDGE_INIT_W], F + Fe, 0, wxT, ldw, H, F};
       tj.job[1] = TransposeJob{params[CGR_PARAM_E2N_W(D)], F + H, 0, wxT + H, ldw, H, F};

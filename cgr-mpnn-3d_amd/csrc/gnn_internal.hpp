@@ -165,9 +165,13 @@ B3Cols image_cols(const Dims& d, int n);
 // the forward weight images are packed into its arena by every call (the weights may have changed
 // by any route: an optimizer writing through raw pointers, a replayed captured step), unless the
 // caller hands pre-packed ones (cgr_gnn_pack_images) and vouches for their freshness.
+// headless (cgr_gnn_encode / _encode_predict): the forward ends in the pool without the ffn
+// head; its `y` argument is the caller's g_out [B, H], and the readout-backward image is packed
+// unscaled for every pooling mode (the headless backward reads a materialised dzn).
 struct FwdMode {
   bool eval = false;
   const void* images = nullptr;
+  bool headless = false;
 };
 struct ImageLayout {
   size_t b3x, b3rof, b3lf[CGR_MAX_DEPTH], bytes;

@@ -55,6 +55,12 @@ hipError_t pool_head_fwd(const float* hn, int Hp, const int* gptr, int64_t B, in
                          const float* inv_cnt = nullptr, int* pool_arg = nullptr,
                          bool pool_first = false);
 
+// the same pool without the head (cgr_gnn_encode): g as pool_head_fwd writes it (same summation
+// order, record and scaling) and g_out [B, H], row stride H (any alignment); no y
+hipError_t pool_only_fwd(const float* hn, int Hp, const int* gptr, int64_t B, int H, float* g,
+                         float* g_out, hipStream_t st, const float* inv_cnt = nullptr,
+                         int* pool_arg = nullptr, bool pool_first = false);
+
 // mean aggregation / pooling factors: inv_deg[v] = 1 / max(in-degree, 1) from the dst CSR,
 // inv_cnt[b] = 1 / max(nodes of graph b, 1) (either nullable: not computed)
 hipError_t mean_scales(const int* dst_ptr, int64_t N, const int* gptr, int64_t B, float* inv_deg,
@@ -76,6 +82,13 @@ hipError_t readout_act_bwd(const float* dy, const float* wf, const int* node_gra
                            const float* hn, const float* zn, int64_t N, int H, int Hp, int act,
                            float* dzn, void* img, hipStream_t st, const float* gscale = nullptr,
                            const int* pool_arg = nullptr, const float* gpool = nullptr);
+// the same from a general cotangent of the pooled embedding (cgr_gnn_encode_backward): the
+// upstream value of dzn[v, n] is dg[graph(v) * H + n] (fp32, row stride H) in place of
+// dy[graph(v)] * wf[n]; gscale, the max-pool pick and the activation follow in the same order
+hipError_t readout_act_bwd_dg(const float* dg, const int* node_graph, const float* hn,
+                              const float* zn, int64_t N, int H, int Hp, int act, float* dzn,
+                              void* img, hipStream_t st, const float* gscale = nullptr,
+                              const int* pool_arg = nullptr, const float* gpool = nullptr);
 
 struct LayerBwdArgs {
   // dh_{l+1}: top layer (l == D-1, layer_act_bwd): ds[dst_s[i]]; below (the fused dm GEMM,

@@ -29,6 +29,9 @@
 extern "C" {
 #endif
 
+/* ABI 9.  The headless entry points (cgr_gnn_encode, _encode_backward, _encode_input_grads,
+ * _encode_predict) were added within ABI 9: they change no existing signature, struct or
+ * behaviour, so a binding written against the earlier ABI 9 keeps working. */
 #define CGR_ABI_VERSION 9
 #define CGR_MAX_DEPTH 32
 
@@ -222,6 +225,37 @@ int cgr_gnn_predict(const cgr_gnn_config* cfg, const float* const* params,
                     const cgr_batch* batch, const float* dropout_p, uint64_t seed,
                     uint64_t* rng_counter, int32_t training, const void* images, void* arena,
                     float* y, void* stream);
+
+/* The encoder without the ffn head (no reference entry point: the reference reaches the same
+ * value with a forward hook on, or one line around, `self.pooling_fn(h, batch)`, GNN.py:110).
+ * cgr_gnn_encode is cgr_gnn_forward up to and including the pooling: it fills `arena` the same way
+ * (same layout, same dropout keying and counter advance) and writes the pooled graph embedding --
+ * the learned reaction fingerprint -- to `g_out`, device [B, hidden] fp32 with row stride `hidden`
+ * (no alignment required); no `y` is computed.  cgr_gnn_encode_backward is the reverse mode from a
+ * general cotangent `dg`, device [B, hidden] fp32 contiguous, = dLoss/dg: every encoder gradient
+ * of the table `grads`; cgr_gnn_encode_input_grads and cgr_gnn_encode_predict are the headless
+ * forms of cgr_gnn_input_grads and cgr_gnn_predict.  All other arguments, the workspace, the
+ * bucket events (bucket 0 then holds edge_to_node only) and the call order are those of the fused
+ * calls.  The ffn.weight / ffn.bias entries of `params` and `grads` may be NULL and are never
+ * read or written: any head (multi-target, an MLP) runs on g_out outside this library.
+ * An arena remembers which forward filled it: cgr_gnn_backward / cgr_gnn_input_grads refuse an
+ * arena of cgr_gnn_encode and cgr_gnn_encode_backward / _encode_input_grads one of
+ * cgr_gnn_forward (nothing enqueued; cgr_last_error says why).  Both precision modes. */
+int cgr_gnn_encode(const cgr_gnn_config* cfg, const float* const* params, const cgr_batch* batch,
+                   const float* dropout_p, uint64_t seed, uint64_t* rng_counter, int32_t training,
+                   void* arena, float* g_out, void* stream);
+int cgr_gnn_encode_backward(const cgr_gnn_config* cfg, const float* const* params,
+                            const cgr_batch* batch, const float* dropout_p, uint64_t seed,
+                            int32_t training, const void* arena, const float* dg,
+                            float* const* grads, void* workspace, void* const* bucket_events,
+                            void* stream);
+int cgr_gnn_encode_input_grads(const cgr_gnn_config* cfg, const float* const* params,
+                               const cgr_batch* batch, const void* arena, const float* dg,
+                               void* workspace, float* dx, float* dedge_attr, void* stream);
+int cgr_gnn_encode_predict(const cgr_gnn_config* cfg, const float* const* params,
+                           const cgr_batch* batch, const float* dropout_p, uint64_t seed,
+                           uint64_t* rng_counter, int32_t training, const void* images,
+                           void* arena, float* g_out, void* stream);
 
 /* Sticky device-side conditions of `device` (no reference counterpart: the reference's autograd
  * cannot fail this way), read from pinned host memory the kernels write -- no device sync, so a

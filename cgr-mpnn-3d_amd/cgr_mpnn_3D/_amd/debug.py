@@ -8,19 +8,25 @@ import ctypes
 import torch
 
 from . import native
-from .functional import _batch_struct, _dropout_array, _param_table, make_config
+from .functional import (_LEVEL_CALLS, LEVEL_FUSED, LEVEL_NODES, LEVEL_POOLED, _batch_struct,
+                         _dropout_array, _param_table, make_config)
 
 
 class ArenaRun:
     def __init__(self, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, params,
                  dropout_ps=None, seed=0, training=False, prepare_backward=True,
-                 rng_counter=None, encode=False, g_out=None):
+                 rng_counter=None, encode=False, g_out=None, nodes=False, n_out=None):
         """rng_counter: optional device int64 tensor [1], the dropout counter the forward reads
         and advances when any layer drops (GNN._cgr_rng_counter's role); None: the key is seed.
         encode: the headless forward (cgr_gnn_encode; the ffn slots of `params` may be None):
         self.g_out [B, H] instead of self.y -- written into `g_out` when the caller passes a
         buffer (any float32 tensor whose storage holds B * H floats from its data pointer) -- and
-        backward / input_grads then take dg [B, H]."""
+        backward / input_grads then take dg [B, H].
+        nodes: the nodes-level forward (cgr_gnn_encode_nodes; ffn slots may be None, the config's
+        pooling takes no part): self.n_out [N, H] -- written into `n_out` when the caller passes a
+        buffer holding N * H floats from its data pointer -- and backward / input_grads take
+        dn [N, H]."""
+        assert not (encode and nodes), "one output level per run"
         lib = native.load()
         self.cfg = make_config(*cfg_tuple)
         self.N, self.E, self.B = int(x.shape[0]), int(edge_index.shape[1]), int(num_graphs)
@@ -30,12 +36,17 @@ class ArenaRun:
         nbytes = lib.cgr_gnn_arena_bytes(ctypes.byref(self.cfg), self.N, self.E, self.B)
         self.arena = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.encode = bool(encode)
-        if self.encode:
-            self.y = None
-            self.g_out = g_out if g_out is not None else torch.empty(
+        self.nodes = bool(nodes)
+        self.level = LEVEL_NODES if nodes else LEVEL_POOLED if encode else LEVEL_FUSED
+        self.y = None
+        if self.nodes:
+            self.n_out = out = n_out if n_out is not None else torch.empty(
+                self.N, self.H, dtype=torch.float32, device=dev)
+        elif self.encode:
+            self.g_out = out = g_out if g_out is not None else torch.empty(
                 self.B, self.H, dtype=torch.float32, device=dev)
         else:
-            self.y = torch.empty(self.B, dtype=torch.float32, device=dev)
+            self.y = out = torch.empty(self.B, dtype=torch.float32, device=dev)
         self._keep = (x, edge_index, edge_attr, batch, graph_ptr, params, rng_counter)
         self.bs = _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, self.B)
         self.dropout_ps, self.seed, self.training = dropout_ps, seed, training
@@ -43,12 +54,12 @@ class ArenaRun:
         self.flags = (native.TRAIN_DROPOUT if training else 0) | (
             native.TRAIN_FOR_BACKWARD if prepare_backward else 0)
         with native.device_guard(dev):
-            entry = lib.cgr_gnn_encode if self.encode else lib.cgr_gnn_forward
+            entry = getattr(lib, _LEVEL_CALLS[self.level][0])
             native.check(entry(
                 ctypes.byref(self.cfg), _param_table(params), ctypes.byref(self.bs),
                 _dropout_array(dropout_ps, self.cfg.depth), ctypes.c_uint64(seed),
                 native.ptr(rng_counter), self.flags, native.ptr(self.arena),
-                native.ptr(self.g_out if self.encode else self.y), native.stream_ptr(dev)))
+                native.ptr(out), native.stream_ptr(dev)))
 
     def offset(self, name, index=0):
         lib = native.load()
@@ -91,14 +102,15 @@ class ArenaRun:
         return self.ws[off:off + 4 * rows * self.Hp].view(torch.float32).view(rows, self.Hp)
 
     def backward(self, dy, params):
-        """dy [B] (encode: dg [B, H]) -> the gradient list (encode: None in the ffn slots)."""
+        """dy [B] (encode: dg [B, H]; nodes: dn [N, H]) -> the gradient list (encode, nodes: None
+        in the ffn slots)."""
         lib = native.load()
         dev = dy.device
         ws = torch.empty(lib.cgr_gnn_workspace_bytes(ctypes.byref(self.cfg), self.N, self.E,
                                                      self.B), dtype=torch.uint8, device=dev)
         grads = [None if p is None else torch.empty_like(p) for p in params]
         self.ws = ws
-        entry = lib.cgr_gnn_encode_backward if self.encode else lib.cgr_gnn_backward
+        entry = getattr(lib, _LEVEL_CALLS[self.level][1])
         with native.device_guard(dev):
             native.check(entry(
                 ctypes.byref(self.cfg), _param_table(params), ctypes.byref(self.bs),
@@ -108,15 +120,16 @@ class ArenaRun:
         return grads
 
     def input_grads(self, dy, params, ws):
-        """cgr_gnn_input_grads (encode: cgr_gnn_encode_input_grads, dy = dg) on this arena with
-        workspace `ws` -> (dx, dedge_attr)."""
+        """cgr_gnn_input_grads (encode: cgr_gnn_encode_input_grads, dy = dg; nodes:
+        cgr_gnn_encode_nodes_input_grads, dy = dn) on this arena with workspace `ws` ->
+        (dx, dedge_attr)."""
         lib = native.load()
         dev = dy.device
         F_ = self.cfg.num_node_features
         Fe = self.cfg.num_edge_features
         dx = torch.empty(self.N, F_, device=dev)
         de = torch.empty(self.E, Fe, device=dev) if Fe else None
-        entry = lib.cgr_gnn_encode_input_grads if self.encode else lib.cgr_gnn_input_grads
+        entry = getattr(lib, _LEVEL_CALLS[self.level][2])
         with native.device_guard(dev):
             native.check(entry(
                 ctypes.byref(self.cfg), _param_table(params), ctypes.byref(self.bs),

@@ -1,5 +1,6 @@
 """autograd bridge: ``GNN.forward`` / backward -> ``cgr_gnn_forward`` / ``cgr_gnn_backward``, and
-``GNN.encode`` (the model without its ffn head) -> ``cgr_gnn_encode`` / ``cgr_gnn_encode_backward``.
+``GNN.encode`` (the model without its ffn head) -> ``cgr_gnn_encode`` / ``cgr_gnn_encode_backward``,
+``GNN.encode_nodes`` (without its pooling either) -> ``cgr_gnn_encode_nodes`` / ``_backward``.
 
 The whole model step is ONE native call each way (≈25 kernel launches enqueued from C++), so the
 host cost per training step is two ctypes calls plus a few caching-allocator allocations; every
@@ -16,6 +17,23 @@ import torch
 
 from . import config as _config
 from . import native
+
+
+# The output level of a native call (gnn_internal.hpp's OutLevel): what the forward returns and so
+# what cotangent its backward takes -- the fused y [B], the pooled g [B, H] or the per-atom
+# hn [N, H] -- and per level its (forward, backward, input-gradients, predict) entry points.
+LEVEL_FUSED, LEVEL_POOLED, LEVEL_NODES = 0, 1, 2
+_LEVEL_CALLS = (
+    ("cgr_gnn_forward", "cgr_gnn_backward", "cgr_gnn_input_grads", "cgr_gnn_predict"),
+    ("cgr_gnn_encode", "cgr_gnn_encode_backward", "cgr_gnn_encode_input_grads",
+     "cgr_gnn_encode_predict"),
+    ("cgr_gnn_encode_nodes", "cgr_gnn_encode_nodes_backward", "cgr_gnn_encode_nodes_input_grads",
+     "cgr_gnn_encode_nodes_predict"),
+)
+
+
+def _out_shape(level, N, B, H):
+    return (B, (B, H), (N, H))[level]
 
 
 def make_config(num_node_features, num_edge_features, hidden, depth, act_code, learnable_skip,
@@ -145,10 +163,12 @@ def read_status(arena, cfg, N, E, B) -> int:
     return int(arena[off:off + 4].view(torch.int32).item())
 
 
-def _function_forward(ctx, headless, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr,
+def _function_forward(ctx, level, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr,
                       num_graphs, dropout_ps, seed, rng_counter, training, bucket_hook, params):
-    """forward of GNNFunction (cgr_gnn_forward -> y [B]) and, headless, of GNNEncodeFunction
-    (cgr_gnn_encode -> g [B, H]; the ffn slots of `params` are None)."""
+    """forward of GNNFunction (LEVEL_FUSED: cgr_gnn_forward -> y [B]), of GNNEncodeFunction
+    (LEVEL_POOLED: cgr_gnn_encode -> g [B, H]) and of GNNNodesFunction (LEVEL_NODES:
+    cgr_gnn_encode_nodes -> hn [N, H]); below the fused level the ffn slots of `params` are
+    None."""
     lib = native.load()
     cfg_tuple = resolve_config_tuple(cfg_tuple)  # the mode of this forward AND its backward
     cfg = make_config(*cfg_tuple)
@@ -156,7 +176,7 @@ def _function_forward(ctx, headless, cfg_tuple, x, edge_index, edge_attr, batch,
     dev = x.device
     arena_bytes = _memo_bytes(_ARENA_BYTES, lib.cgr_gnn_arena_bytes, cfg, cfg_tuple, N, E, B)
     arena = torch.empty(arena_bytes, dtype=torch.uint8, device=dev)
-    y = torch.empty((B, cfg.hidden) if headless else B, dtype=torch.float32, device=dev)
+    y = torch.empty(_out_shape(level, N, B, cfg.hidden), dtype=torch.float32, device=dev)
     bs = _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, B)
     ptab = _param_table(params)
     dps = _dropout_array(dropout_ps, cfg.depth)
@@ -167,13 +187,18 @@ def _function_forward(ctx, headless, cfg_tuple, x, edge_index, edge_attr, batch,
         ctx.needs_input_grad[3]
     flags = (native.TRAIN_DROPOUT if training else 0) | (
         native.TRAIN_FOR_BACKWARD if want_bwd else 0)
-    if headless and want_bwd and (bucket_hook is not None or
-                                  _config.grad_bucket_hook is not None):
+    if level != LEVEL_FUSED and want_bwd and (bucket_hook is not None or
+                                              _config.grad_bucket_hook is not None):
+        if level == LEVEL_NODES:
+            raise NotImplementedError(
+                "cgr_mpnn_3D: GNN.encode_nodes with a gradient-bucket hook: the torch-side "
+                "readout's and head's gradients are not in the flat bucket buffer the hook "
+                "all-reduces (data-parallel node embeddings are not supported)")
         raise NotImplementedError(
             "cgr_mpnn_3D: GNN.encode / a custom ffn head with a gradient-bucket hook: the "
             "torch-side head's gradients are not in the flat bucket buffer the hook "
             "all-reduces (data-parallel fingerprints are not supported)")
-    entry = lib.cgr_gnn_encode if headless else lib.cgr_gnn_forward
+    entry = getattr(lib, _LEVEL_CALLS[level][0])
     with native.device_guard(dev):
         native.check(entry(ctypes.byref(cfg), ptab, ctypes.byref(bs), dps,
                            ctypes.c_uint64(seed), native.ptr(rng_counter),
@@ -192,9 +217,10 @@ def _function_forward(ctx, headless, cfg_tuple, x, edge_index, edge_attr, batch,
     return y
 
 
-def _function_backward(ctx, headless, dy):
-    """backward of GNNFunction (dy [B]) and, headless, of GNNEncodeFunction (dy = dg [B, H]: the
-    ffn slots of the returned gradients are None)."""
+def _function_backward(ctx, level, dy):
+    """backward of GNNFunction (dy [B]), of GNNEncodeFunction (dy = dg [B, H]) and of
+    GNNNodesFunction (dy = dn [N, H]); below the fused level the ffn slots of the returned
+    gradients are None."""
     lib = native.load()
     x, edge_index, edge_attr, batch, graph_ptr, arena, *params = ctx.saved_tensors
     native.raise_device_errors(x.device, clear=False)  # an earlier backward's timeout
@@ -217,9 +243,9 @@ def _function_backward(ctx, headless, dy):
     evtab = None
     if events is not None:
         evtab = (c_void_p * len(events))(*[e.cuda_event for e in events])
-    if headless:
+    if level != LEVEL_FUSED:
         grads = [None if p is None else g for p, g in zip(params, grads)]
-    entry = lib.cgr_gnn_encode_backward if headless else lib.cgr_gnn_backward
+    entry = getattr(lib, _LEVEL_CALLS[level][1])
     with native.device_guard(dev):
         native.check(entry(
             ctypes.byref(cfg), _param_table(params), ctypes.byref(bs),
@@ -233,7 +259,7 @@ def _function_backward(ctx, headless, dy):
             dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
         if ctx.needs_input_grad[3]:
             dea = torch.empty(edge_attr.shape, dtype=torch.float32, device=dev)
-        entry = lib.cgr_gnn_encode_input_grads if headless else lib.cgr_gnn_input_grads
+        entry = getattr(lib, _LEVEL_CALLS[level][2])
         with native.device_guard(dev):
             native.check(entry(
                 ctypes.byref(cfg), _param_table(params), ctypes.byref(bs), native.ptr(arena),
@@ -254,13 +280,13 @@ class GNNFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
                 dropout_ps, seed, rng_counter, training, bucket_hook, *params):
-        return _function_forward(ctx, False, cfg_tuple, x, edge_index, edge_attr, batch,
+        return _function_forward(ctx, LEVEL_FUSED, cfg_tuple, x, edge_index, edge_attr, batch,
                                  graph_ptr, num_graphs, dropout_ps, seed, rng_counter, training,
                                  bucket_hook, params)
 
     @staticmethod
     def backward(ctx, dy):
-        return _function_backward(ctx, False, dy)
+        return _function_backward(ctx, LEVEL_FUSED, dy)
 
 
 class GNNEncodeFunction(torch.autograd.Function):
@@ -271,13 +297,30 @@ class GNNEncodeFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
                 dropout_ps, seed, rng_counter, training, bucket_hook, *params):
-        return _function_forward(ctx, True, cfg_tuple, x, edge_index, edge_attr, batch,
+        return _function_forward(ctx, LEVEL_POOLED, cfg_tuple, x, edge_index, edge_attr, batch,
                                  graph_ptr, num_graphs, dropout_ps, seed, rng_counter, training,
                                  bucket_hook, params)
 
     @staticmethod
     def backward(ctx, dg):
-        return _function_backward(ctx, True, dg)
+        return _function_backward(ctx, LEVEL_POOLED, dg)
+
+
+class GNNNodesFunction(torch.autograd.Function):
+    """hn[N, H] = act(edge_to_node(cat[x, a_D])): the model without its pooling and its ffn head
+    (cgr_gnn_encode_nodes / _encode_nodes_backward / _encode_nodes_input_grads).  `params` is the
+    C-ABI table with None in the two ffn slots; their gradients come back as None."""
+
+    @staticmethod
+    def forward(ctx, cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
+                dropout_ps, seed, rng_counter, training, bucket_hook, *params):
+        return _function_forward(ctx, LEVEL_NODES, cfg_tuple, x, edge_index, edge_attr, batch,
+                                 graph_ptr, num_graphs, dropout_ps, seed, rng_counter, training,
+                                 bucket_hook, params)
+
+    @staticmethod
+    def backward(ctx, dn):
+        return _function_backward(ctx, LEVEL_NODES, dn)
 
 
 # predict arena sizes by (config, N, E, B): a pure function of its key (one ctypes call saved per
@@ -286,13 +329,14 @@ _PREDICT_ARENA_BYTES: dict = {}
 
 
 def gnn_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, dropout_ps,
-                seed, training, params, rng_counter=None, headless=False):
+                seed, training, params, rng_counter=None, level=LEVEL_FUSED):
     """Forward-only GNN (cgr_gnn_predict): no saved activations.  What GNN.forward runs when no
     gradient is wanted (test.py:100-113 under torch.no_grad()).  The weight images are packed
     into the call's own arena by every call: no cache to go stale when an optimizer (FusedAdam,
     a replayed captured step) updates the parameters through raw pointers, and no buffer shared
-    with a predict still running on another stream.  headless: cgr_gnn_encode_predict, the pooled
-    embedding g [B, H] (gnn_encode_predict)."""
+    with a predict still running on another stream.  level: LEVEL_POOLED is
+    cgr_gnn_encode_predict, the pooled embedding g [B, H] (gnn_encode_predict); LEVEL_NODES
+    cgr_gnn_encode_nodes_predict, the node embedding hn [N, H] (gnn_encode_nodes_predict)."""
     lib = native.load()
     cfg_tuple = resolve_config_tuple(cfg_tuple)
     cfg = make_config(*cfg_tuple)
@@ -308,9 +352,9 @@ def gnn_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graph
             _PREDICT_ARENA_BYTES.clear()
         _PREDICT_ARENA_BYTES[key] = nbytes
     arena = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    y = torch.empty((B, cfg.hidden) if headless else B, dtype=torch.float32, device=dev)
+    y = torch.empty(_out_shape(level, N, B, cfg.hidden), dtype=torch.float32, device=dev)
     bs = _batch_struct(x, edge_index, edge_attr, batch, graph_ptr, B)
-    entry = lib.cgr_gnn_encode_predict if headless else lib.cgr_gnn_predict
+    entry = getattr(lib, _LEVEL_CALLS[level][3])
     with native.device_guard(dev):
         native.check(entry(
             ctypes.byref(cfg), _param_table(params), ctypes.byref(bs),
@@ -355,4 +399,22 @@ def gnn_encode_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, nu
                        dropout_ps, seed, training, params, rng_counter=None):
     """Forward-only fingerprint (cgr_gnn_encode_predict): gnn_predict without the head."""
     return gnn_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
-                       dropout_ps, seed, training, params, rng_counter=rng_counter, headless=True)
+                       dropout_ps, seed, training, params, rng_counter=rng_counter,
+                       level=LEVEL_POOLED)
+
+
+def gnn_encode_nodes(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, dropout_ps,
+                     seed, training, params, bucket_hook=None, rng_counter=None):
+    """The differentiable per-atom embedding hn [N, H] (GNNNodesFunction); `params` in the C-ABI
+    table order with None in the ffn slots."""
+    return GNNNodesFunction.apply(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr,
+                                  num_graphs, dropout_ps, seed, rng_counter, training,
+                                  bucket_hook, *params)
+
+
+def gnn_encode_nodes_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
+                             dropout_ps, seed, training, params, rng_counter=None):
+    """Forward-only node embedding (cgr_gnn_encode_nodes_predict)."""
+    return gnn_predict(cfg_tuple, x, edge_index, edge_attr, batch, graph_ptr, num_graphs,
+                       dropout_ps, seed, training, params, rng_counter=rng_counter,
+                       level=LEVEL_NODES)

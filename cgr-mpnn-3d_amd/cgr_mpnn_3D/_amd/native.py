@@ -109,6 +109,19 @@ SIGNATURES = [
     ("cgr_gnn_encode_predict", c_int32,
      [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), POINTER(c_float), c_uint64,
       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the nodes level (added within ABI 9): n_out / dn [N, H], the encode forms argument for argument
+    ("cgr_gnn_encode_nodes", c_int32,
+     [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), POINTER(c_float), c_uint64,
+      c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("cgr_gnn_encode_nodes_backward", c_int32,
+     [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), POINTER(c_float), c_uint64,
+      c_int32, c_void_p, c_void_p, POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p]),
+    ("cgr_gnn_encode_nodes_input_grads", c_int32,
+     [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p]),
+    ("cgr_gnn_encode_nodes_predict", c_int32,
+     [POINTER(CgrGnnConfig), POINTER(c_void_p), POINTER(CgrBatch), POINTER(c_float), c_uint64,
+      c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("cgr_segment_sum", c_int32,
      [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     ("cgr_dmpnn_conv_scratch_bytes", c_int64, [c_int64, c_int64, c_int64]),

@@ -69,7 +69,8 @@ def pooling_code(fn) -> int:
     raise NotImplementedError(
         f"cgr_mpnn_3D (MI355X): pooling_fn {getattr(fn, '__name__', fn)!r} has no native head; "
         "supported are global_add_pool (the reference default), global_mean_pool and "
-        "global_max_pool")
+        "global_max_pool; any other readout composes in PyTorch on the per-atom embedding, "
+        "ffn(pooling_fn(model.encode_nodes(data), data.batch))")
 
 
 def aggregation_code(aggr) -> int:

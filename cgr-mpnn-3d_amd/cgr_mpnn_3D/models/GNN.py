@@ -8,7 +8,9 @@ given ``torch.manual_seed`` is identical (parameters are created in the referenc
 What differs is underneath: ``GNN.forward`` is one call into ``libcgr_mpnn3d.so`` (HIP kernels for
 gfx950) through ``cgr_mpnn_3D._amd.functional.GNNFunction``; the backward is one more call.
 ``GNN.encode`` returns the pooled reaction fingerprint from the same kernels without the head,
-and a replaced ``ffn`` (any module) runs in PyTorch on top of it, as in the reference.  There
+and a replaced ``ffn`` (any module) runs in PyTorch on top of it, as in the reference;
+``GNN.encode_nodes`` returns the per-atom embedding one level further down, the input of
+``pooling_fn``, for any readout composed in PyTorch.  There
 is no CPU/PyTorch fallback: CPU tensors or a missing library raise.  ``torch_geometric`` is not
 required; PyG ``Batch``/``Data`` objects are accepted by duck typing (``x``, ``edge_index``,
 ``edge_attr``, ``batch`` and optionally ``ptr`` / ``num_graphs``).
@@ -34,7 +36,9 @@ import torch.nn.functional as F
 
 from .._amd import config as _config
 from .._amd import native
-from .._amd.functional import gnn_encode, gnn_encode_predict, gnn_forward, gnn_predict
+from .._amd.functional import (LEVEL_FUSED, LEVEL_NODES, LEVEL_POOLED, gnn_encode,
+                               gnn_encode_nodes, gnn_encode_nodes_predict, gnn_encode_predict,
+                               gnn_forward, gnn_predict)
 from .._amd.pool import (aggregation_code, global_add_pool, global_max_pool, global_mean_pool,
                          pooling_code)
 
@@ -215,16 +219,17 @@ class GNN(nn.Module):
             ff.in_features == self._modules["edge_to_node"].out_features
 
     # -- forward -------------------------------------------------------------------------------
-    def _cgr_run(self, data, head):
-        """Input handling and checks shared by ``forward`` (head=True: the fused call, y [B]) and
-        ``encode`` (head=False: the headless call, g [B, H]), then the native call: its predict
-        form when no gradient is wanted."""
+    def _cgr_run(self, data, level):
+        """Input handling and checks shared by ``forward`` (LEVEL_FUSED: the fused call, y [B]),
+        ``encode`` (LEVEL_POOLED: the headless call, g [B, H]) and ``encode_nodes`` (LEVEL_NODES:
+        hn [N, H]), then the native call: its predict form when no gradient is wanted."""
         x, edge_index, edge_attr, batch = data.x, data.edge_index, data.edge_attr, data.batch
         if not x.is_cuda:
             raise RuntimeError(
                 "cgr_mpnn_3D (MI355X) runs on the GPU only: move the model and the batch to "
                 "'cuda' (there is no CPU fallback)")
-        pool = pooling_code(self.pooling_fn)
+        # (the nodes level ends before the pooling: pooling_fn may be any callable, code 0)
+        pool = 0 if level == LEVEL_NODES else pooling_code(self.pooling_fn)
         aggrs = {aggregation_code(conv.aggr) for conv in self._modules["convs"]._modules.values()}
         if len(aggrs) != 1:
             raise NotImplementedError("cgr_mpnn_3D (MI355X): one aggr for every DMPNNConv")
@@ -283,10 +288,10 @@ class GNN(nn.Module):
             if not getattr(self, "_cgr_unpaired_warned", False) and _warn_if_unpaired(edge_index):
                 self._cgr_unpaired_warned = True
 
-        params = self.native_parameters(head)
+        params = self.native_parameters(level == LEVEL_FUSED)
         want_grad = x.requires_grad or edge_attr.requires_grad
         for i, p in enumerate(params):
-            if p is None:  # (encode: the ffn slots)
+            if p is None:  # (encode, encode_nodes: the ffn slots)
                 continue
             if p.dtype != torch.float32 or not p.is_cuda:
                 raise RuntimeError("cgr_mpnn_3D (MI355X): parameters must be fp32 CUDA tensors")
@@ -306,10 +311,10 @@ class GNN(nn.Module):
             # no gradient wanted (test.py / the CLI run under torch.no_grad()): the forward-only
             # path, no saved activations
             # (no autograd here: the raw parameters' data pointers, no detach)
-            run = gnn_predict if head else gnn_encode_predict
+            run = (gnn_predict, gnn_encode_predict, gnn_encode_nodes_predict)[level]
             return run(cfg, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, drop,
                        seed, training, params, rng_counter=counter)
-        run = gnn_forward if head else gnn_encode
+        run = (gnn_forward, gnn_encode, gnn_encode_nodes)[level]
         return run(cfg, x, edge_index, edge_attr, batch, graph_ptr, num_graphs, drop,
                    seed, training, params, self._grad_bucket_hook, rng_counter=counter)
 
@@ -322,8 +327,8 @@ class GNN(nn.Module):
         ``ffn`` do not change this routing (the fused call does not run the module, so they do
         not fire for the default head): read the fingerprint with ``encode``."""
         if self._fused_head():
-            return self._cgr_run(data, True)
-        return self.ffn(self._cgr_run(data, False)).squeeze(-1)
+            return self._cgr_run(data, LEVEL_FUSED)
+        return self.ffn(self._cgr_run(data, LEVEL_POOLED)).squeeze(-1)
 
     def encode(self, data):
         """The learned reaction fingerprint ``pooling_fn(h, batch)`` [B, H] (the input of ``ffn``,
@@ -331,7 +336,17 @@ class GNN(nn.Module):
         ``edge_attr``.  Same input handling, dropout keying and counter advance as ``forward``;
         under ``torch.no_grad()`` or when nothing requires grad, the forward-only form.  ``ffn``
         takes no part, so it may be any module."""
-        return self._cgr_run(data, False)
+        return self._cgr_run(data, LEVEL_POOLED)
+
+    def encode_nodes(self, data):
+        """The per-atom embedding ``act(edge_to_node(cat[x, a_D]))`` [N, H] (the input of
+        ``pooling_fn``, GNN.py:105-108), differentiable with respect to every encoder parameter,
+        ``x`` and ``edge_attr``.  Same input handling, dropout keying and counter advance as
+        ``forward``; under ``torch.no_grad()`` or when nothing requires grad, the forward-only
+        form.  ``pooling_fn`` and ``ffn`` take no part, so either may be anything -- a readout the
+        native pools cannot express composes on it in PyTorch:
+        ``ffn(my_pool(model.encode_nodes(data), data.batch))``."""
+        return self._cgr_run(data, LEVEL_NODES)
 
 
 class DMPNNConv(nn.Module):

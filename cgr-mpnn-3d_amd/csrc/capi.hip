@@ -33,21 +33,38 @@ static std::unordered_map<const void*, int> g_arena_mode;
 // current generation (otherwise it silently returned garbage)
 static std::unordered_map<const void*, uint64_t> g_arena_gen;
 static std::unordered_map<const void*, std::pair<const void*, uint64_t>> g_ws_backward;
-// ... and whether it was a headless forward (cgr_gnn_encode: no ffn head, the readout-backward
-// image unscaled for every pooling mode): the fused backward / input gradients refuse a headless
-// arena, the encode ones a fused arena
-static std::unordered_map<const void*, bool> g_arena_headless;
-static void note_forward(const void* arena, int flags, int mode = -1, bool headless = false) {
+// ... and its output level (gnn_internal.hpp: the fused y of cgr_gnn_forward, the pooled g of
+// cgr_gnn_encode, the nodes of cgr_gnn_encode_nodes; below the fused level the readout-backward
+// image is unscaled for every pooling mode, and the nodes level leaves the pooling state
+// unwritten): every backward / input-gradients entry refuses an arena of another level
+static std::unordered_map<const void*, OutLevel> g_arena_level;
+static void note_forward(const void* arena, int flags, int mode = -1,
+                         OutLevel level = OutLevel::Fused) {
   std::lock_guard<std::mutex> lk(g_arena_mu);
   g_arena_flags[arena] = flags;
   g_arena_mode[arena] = mode;
-  g_arena_headless[arena] = headless;
+  g_arena_level[arena] = level;
   ++g_arena_gen[arena];
 }
-static bool forward_headless(const void* arena) {
+static OutLevel forward_level(const void* arena) {
   std::lock_guard<std::mutex> lk(g_arena_mu);
-  const auto it = g_arena_headless.find(arena);
-  return it != g_arena_headless.end() && it->second;
+  const auto it = g_arena_level.find(arena);
+  return it == g_arena_level.end() ? OutLevel::Fused : it->second;
+}
+// the calls of one output level and the names of its output and cotangent, for the messages
+struct LevelCalls {
+  const char *fwd, *bwd, *igr, *pred, *out, *up, *what;
+};
+static const LevelCalls& calls_of(OutLevel level) {
+  static const LevelCalls k[3] = {
+      {"cgr_gnn_forward", "cgr_gnn_backward", "cgr_gnn_input_grads", "cgr_gnn_predict", "y", "dy",
+       "with the ffn head"},
+      {"cgr_gnn_encode", "cgr_gnn_encode_backward", "cgr_gnn_encode_input_grads",
+       "cgr_gnn_encode_predict", "g_out", "dg", "headless, no ffn head"},
+      {"cgr_gnn_encode_nodes", "cgr_gnn_encode_nodes_backward", "cgr_gnn_encode_nodes_input_grads",
+       "cgr_gnn_encode_nodes_predict", "n_out", "dn",
+       "per-atom embeddings, no pooling or ffn head"}};
+  return k[(int)level];
 }
 static int forward_mode(const void* arena) {
   std::lock_guard<std::mutex> lk(g_arena_mu);
@@ -79,10 +96,10 @@ hipError_t pack_forward_images(const Dims& d, const float* const* params, const 
 int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch* b,
                       const float* dropout_p, uint64_t seed, int training, const void* arena,
                       const float* dy, float* const* grads, void* workspace,
-                      hipEvent_t const* bucket_events, hipStream_t st, bool headless);
+                      hipEvent_t const* bucket_events, hipStream_t st, OutLevel level);
 int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* arena,
                          const float* dy, void* workspace, float* dx, float* de, hipStream_t st,
-                         bool headless);
+                         OutLevel level);
 
 Dims make_dims(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B) {
   Dims d;
@@ -463,6 +480,11 @@ int64_t cgr_gnn_workspace_offset(const cgr_gnn_config* cfg, int64_t N, int64_t E
     return (int64_t)(W.dpre + (size_t)index * 4 * (size_t)d.E * (size_t)d.Hp);
   if (n == "dpre0") return (int64_t)W.dh0;
   if (n == "ds") return (int64_t)W.ds;
+  // "dzn_main": dzn [N, Hp] where the backward materialises it in fp32 on the caller's stream for
+  // the readout NT -- below the fused level (cgr_gnn_encode_backward,
+  // cgr_gnn_encode_nodes_backward) and under max pooling.  ("dzn" stays unknown: the fused add /
+  // mean backward on the split-bf16 path never stores it.)
+  if (n == "dzn_main") return (int64_t)W.dzn;
   return -1;
 }
 
@@ -481,13 +503,15 @@ int cgr_graph_prep(const cgr_gnn_config* cfg, const cgr_batch* b, void* arena, v
   return cgr_graph_prep_impl(pa, (hipStream_t)stream);
 }
 
-// the ffn entries of a parameter / gradient table: NULL allowed in the headless (encode) calls
+// the ffn entries of a parameter / gradient table: NULL allowed below the fused level (the
+// encode and encode_nodes calls)
 static bool is_ffn_entry(const cgr_gnn_config* cfg, int i) {
   return i == CGR_PARAM_FFN_W(cfg->depth) || i == CGR_PARAM_FFN_B(cfg->depth);
 }
 
-// cgr_gnn_forward (y [B]) / cgr_gnn_encode (headless: out = g_out [B, H])
-static int forward_entry(bool headless, const cgr_gnn_config* cfg, const float* const* params,
+// cgr_gnn_forward (y [B]) / cgr_gnn_encode (out = g_out [B, H]) / cgr_gnn_encode_nodes (out =
+// n_out [N, H])
+static int forward_entry(OutLevel level, const cgr_gnn_config* cfg, const float* const* params,
                          const cgr_batch* b, const float* dropout_p, uint64_t seed,
                          uint64_t* rng_counter, int32_t training, void* arena, float* out,
                          void* stream) {
@@ -496,9 +520,9 @@ static int forward_entry(bool headless, const cgr_gnn_config* cfg, const float* 
   if (rc) return rc;
   rc = validate_batch(cfg, b);
   if (rc) return rc;
+  const bool headless = level != OutLevel::Fused;
   CGR_CHECK(params != nullptr && arena != nullptr && out != nullptr,
-            headless ? "cgr: params / arena / g_out must not be NULL"
-                     : "cgr: params / arena / y must not be NULL");
+            std::string("cgr: params / arena / ") + calls_of(level).out + " must not be NULL");
   CGR_CHECK((training & ~(CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)) == 0,
             "cgr: unknown `training` bits (CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)");
   const int np = cgr_gnn_num_params(cfg);
@@ -508,35 +532,44 @@ static int forward_entry(bool headless, const cgr_gnn_config* cfg, const float* 
   const Dims d = make_dims(cfg, b->num_nodes, b->num_edges, b->num_graphs);
   note_forward(arena, -1);  // not usable by a backward unless the forward below succeeds
   FwdMode m;
-  m.headless = headless;
+  m.level = level;
   const int r = gnn_forward_impl(d, params, b, dropout_p, seed, rng_counter, training, arena, out,
                                  (hipStream_t)stream, m);
-  if (r == 0) note_forward(arena, training, cfg->precision, headless);
+  if (r == 0) note_forward(arena, training, cfg->precision, level);
   return r;
 }
 
 int cgr_gnn_forward(const cgr_gnn_config* cfg, const float* const* params, const cgr_batch* b,
                     const float* dropout_p, uint64_t seed, uint64_t* rng_counter,
                     int32_t training, void* arena, float* y, void* stream) {
-  return forward_entry(false, cfg, params, b, dropout_p, seed, rng_counter, training, arena, y,
-                       stream);
+  return forward_entry(OutLevel::Fused, cfg, params, b, dropout_p, seed, rng_counter, training,
+                       arena, y, stream);
 }
 
 int cgr_gnn_encode(const cgr_gnn_config* cfg, const float* const* params, const cgr_batch* b,
                    const float* dropout_p, uint64_t seed, uint64_t* rng_counter, int32_t training,
                    void* arena, float* g_out, void* stream) {
-  return forward_entry(true, cfg, params, b, dropout_p, seed, rng_counter, training, arena, g_out,
-                       stream);
+  return forward_entry(OutLevel::Pooled, cfg, params, b, dropout_p, seed, rng_counter, training,
+                       arena, g_out, stream);
 }
 
-// cgr_gnn_backward (up = dy [B]) / cgr_gnn_encode_backward (headless: up = dg [B, H])
-static int backward_entry(bool headless, const cgr_gnn_config* cfg, const float* const* params,
+int cgr_gnn_encode_nodes(const cgr_gnn_config* cfg, const float* const* params,
+                         const cgr_batch* b, const float* dropout_p, uint64_t seed,
+                         uint64_t* rng_counter, int32_t training, void* arena, float* n_out,
+                         void* stream) {
+  return forward_entry(OutLevel::Nodes, cfg, params, b, dropout_p, seed, rng_counter, training,
+                       arena, n_out, stream);
+}
+
+// cgr_gnn_backward (up = dy [B]) / cgr_gnn_encode_backward (up = dg [B, H]) /
+// cgr_gnn_encode_nodes_backward (up = dn [N, H])
+static int backward_entry(OutLevel level, const cgr_gnn_config* cfg, const float* const* params,
                           const cgr_batch* b, const float* dropout_p, uint64_t seed,
                           int32_t training, const void* arena, const float* up,
                           float* const* grads, void* workspace, void* const* bucket_events,
                           void* stream) {
-  const std::string fn = headless ? "cgr_gnn_encode_backward" : "cgr_gnn_backward";
-  const std::string fwd = headless ? "cgr_gnn_encode" : "cgr_gnn_forward";
+  const bool headless = level != OutLevel::Fused;
+  const std::string fn = calls_of(level).bwd, fwd = calls_of(level).fwd;
   clear_stale_hip_error();
   int rc = validate_config(cfg);
   if (rc) return rc;
@@ -544,19 +577,18 @@ static int backward_entry(bool headless, const cgr_gnn_config* cfg, const float*
   if (rc) return rc;
   CGR_CHECK(params != nullptr && arena != nullptr && up != nullptr && grads != nullptr &&
                 workspace != nullptr,
-            headless ? "cgr: params / arena / dg / grads / workspace must not be NULL"
-                     : "cgr: params / arena / dy / grads / workspace must not be NULL");
+            std::string("cgr: params / arena / ") + calls_of(level).up +
+                " / grads / workspace must not be NULL");
   CGR_CHECK((training & ~(CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)) == 0,
             "cgr: unknown `training` bits (CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)");
   const int ff = forward_flags(arena);
   CGR_CHECK(ff >= 0 && (ff & CGR_TRAIN_FOR_BACKWARD),
             fn + ": `arena` was not filled by a successful " + fwd + " with "
             "CGR_TRAIN_FOR_BACKWARD set");
-  CGR_CHECK(forward_headless(arena) == headless,
-            headless ? fn + ": `arena` was filled by cgr_gnn_forward (with the ffn head); its "
-                            "backward is cgr_gnn_backward"
-                     : fn + ": `arena` was filled by cgr_gnn_encode (headless, no ffn head); its "
-                            "backward is cgr_gnn_encode_backward");
+  const LevelCalls& own = calls_of(forward_level(arena));  // the arena's own calls
+  CGR_CHECK(forward_level(arena) == level,
+            fn + ": `arena` was filled by " + own.fwd + " (" + own.what + "); its backward is " +
+                own.bwd);
   CGR_CHECK((ff & CGR_TRAIN_DROPOUT) == (training & CGR_TRAIN_DROPOUT),
             fn + ": `training` dropout bit differs from the forward's");
   CGR_CHECK(forward_mode(arena) == cfg->precision,
@@ -574,7 +606,7 @@ static int backward_entry(bool headless, const cgr_gnn_config* cfg, const float*
       CGR_CHECK(bucket_events[i] != nullptr, fn + ": NULL bucket event");
   const int r = gnn_backward_impl(d, params, b, dropout_p, seed, training, arena, up, grads,
                                   workspace, reinterpret_cast<hipEvent_t const*>(bucket_events),
-                                  (hipStream_t)stream, headless);
+                                  (hipStream_t)stream, level);
   if (r == 0) note_backward(arena, workspace);
   return r;
 }
@@ -583,8 +615,8 @@ int cgr_gnn_backward(const cgr_gnn_config* cfg, const float* const* params, cons
                      const float* dropout_p, uint64_t seed, int32_t training, const void* arena,
                      const float* dy, float* const* grads, void* workspace,
                      void* const* bucket_events, void* stream) {
-  return backward_entry(false, cfg, params, b, dropout_p, seed, training, arena, dy, grads,
-                        workspace, bucket_events, stream);
+  return backward_entry(OutLevel::Fused, cfg, params, b, dropout_p, seed, training, arena, dy,
+                        grads, workspace, bucket_events, stream);
 }
 
 int cgr_gnn_encode_backward(const cgr_gnn_config* cfg, const float* const* params,
@@ -592,35 +624,44 @@ int cgr_gnn_encode_backward(const cgr_gnn_config* cfg, const float* const* param
                             int32_t training, const void* arena, const float* dg,
                             float* const* grads, void* workspace, void* const* bucket_events,
                             void* stream) {
-  return backward_entry(true, cfg, params, b, dropout_p, seed, training, arena, dg, grads,
-                        workspace, bucket_events, stream);
+  return backward_entry(OutLevel::Pooled, cfg, params, b, dropout_p, seed, training, arena, dg,
+                        grads, workspace, bucket_events, stream);
 }
 
-// cgr_gnn_input_grads (up = dy [B]) / cgr_gnn_encode_input_grads (headless: up = dg [B, H])
-static int input_grads_entry(bool headless, const cgr_gnn_config* cfg,
+int cgr_gnn_encode_nodes_backward(const cgr_gnn_config* cfg, const float* const* params,
+                                  const cgr_batch* b, const float* dropout_p, uint64_t seed,
+                                  int32_t training, const void* arena, const float* dn,
+                                  float* const* grads, void* workspace,
+                                  void* const* bucket_events, void* stream) {
+  return backward_entry(OutLevel::Nodes, cfg, params, b, dropout_p, seed, training, arena, dn,
+                        grads, workspace, bucket_events, stream);
+}
+
+// cgr_gnn_input_grads (up = dy [B]) / cgr_gnn_encode_input_grads (up = dg [B, H]) /
+// cgr_gnn_encode_nodes_input_grads (up = dn [N, H])
+static int input_grads_entry(OutLevel level, const cgr_gnn_config* cfg,
                              const float* const* params, const cgr_batch* b, const void* arena,
                              const float* up, void* workspace, float* dx, float* dedge_attr,
                              void* stream) {
-  const std::string fn = headless ? "cgr_gnn_encode_input_grads" : "cgr_gnn_input_grads";
-  const std::string fwd = headless ? "cgr_gnn_encode" : "cgr_gnn_forward";
-  const std::string bwd = headless ? "cgr_gnn_encode_backward" : "cgr_gnn_backward";
+  const bool headless = level != OutLevel::Fused;
+  const std::string fn = calls_of(level).igr, fwd = calls_of(level).fwd,
+                    bwd = calls_of(level).bwd;
   clear_stale_hip_error();
   int rc = validate_config(cfg);
   if (rc) return rc;
   rc = validate_batch(cfg, b);
   if (rc) return rc;
   CGR_CHECK(params != nullptr && arena != nullptr && up != nullptr && workspace != nullptr,
-            headless ? "cgr: params / arena / dg / workspace must not be NULL"
-                     : "cgr: params / arena / dy / workspace must not be NULL");
+            std::string("cgr: params / arena / ") + calls_of(level).up +
+                " / workspace must not be NULL");
   const int ff = forward_flags(arena);
   CGR_CHECK(ff >= 0 && (ff & CGR_TRAIN_FOR_BACKWARD),
             fn + ": `arena` was not filled by a successful " + fwd + " with "
             "CGR_TRAIN_FOR_BACKWARD set");
-  CGR_CHECK(forward_headless(arena) == headless,
-            headless ? fn + ": `arena` was filled by cgr_gnn_forward (with the ffn head); its "
-                            "input gradients are cgr_gnn_input_grads"
-                     : fn + ": `arena` was filled by cgr_gnn_encode (headless, no ffn head); its "
-                            "input gradients are cgr_gnn_encode_input_grads");
+  const LevelCalls& own = calls_of(forward_level(arena));  // the arena's own calls
+  CGR_CHECK(forward_level(arena) == level,
+            fn + ": `arena` was filled by " + own.fwd + " (" + own.what +
+                "); its input gradients are " + own.igr);
   CGR_CHECK(forward_mode(arena) == cfg->precision,
             fn + ": the config's precision differs from the mode `arena`'s forward "
             "ran in");
@@ -635,19 +676,29 @@ static int input_grads_entry(bool headless, const cgr_gnn_config* cfg,
               "cgr: NULL parameter pointer");
   const Dims d = make_dims(cfg, b->num_nodes, b->num_edges, b->num_graphs);
   return gnn_input_grads_impl(d, params, arena, up, workspace, dx, dedge_attr,
-                              (hipStream_t)stream, headless);
+                              (hipStream_t)stream, level);
 }
 
 int cgr_gnn_input_grads(const cgr_gnn_config* cfg, const float* const* params,
                         const cgr_batch* b, const void* arena, const float* dy, void* workspace,
                         float* dx, float* dedge_attr, void* stream) {
-  return input_grads_entry(false, cfg, params, b, arena, dy, workspace, dx, dedge_attr, stream);
+  return input_grads_entry(OutLevel::Fused, cfg, params, b, arena, dy, workspace, dx,
+                           dedge_attr, stream);
 }
 
 int cgr_gnn_encode_input_grads(const cgr_gnn_config* cfg, const float* const* params,
                                const cgr_batch* b, const void* arena, const float* dg,
                                void* workspace, float* dx, float* dedge_attr, void* stream) {
-  return input_grads_entry(true, cfg, params, b, arena, dg, workspace, dx, dedge_attr, stream);
+  return input_grads_entry(OutLevel::Pooled, cfg, params, b, arena, dg, workspace, dx,
+                           dedge_attr, stream);
+}
+
+int cgr_gnn_encode_nodes_input_grads(const cgr_gnn_config* cfg, const float* const* params,
+                                     const cgr_batch* b, const void* arena, const float* dn,
+                                     void* workspace, float* dx, float* dedge_attr,
+                                     void* stream) {
+  return input_grads_entry(OutLevel::Nodes, cfg, params, b, arena, dn, workspace, dx, dedge_attr,
+                           stream);
 }
 
 int64_t cgr_gnn_image_bytes(const cgr_gnn_config* cfg) {
@@ -673,8 +724,9 @@ int64_t cgr_gnn_predict_arena_bytes(const cgr_gnn_config* cfg, int64_t N, int64_
   return (int64_t)eval_arena_layout(make_dims(cfg, N, E, B)).bytes;
 }
 
-// cgr_gnn_predict (y [B]) / cgr_gnn_encode_predict (headless: out = g_out [B, H])
-static int predict_entry(bool headless, const cgr_gnn_config* cfg, const float* const* params,
+// cgr_gnn_predict (y [B]) / cgr_gnn_encode_predict (out = g_out [B, H]) /
+// cgr_gnn_encode_nodes_predict (out = n_out [N, H])
+static int predict_entry(OutLevel level, const cgr_gnn_config* cfg, const float* const* params,
                          const cgr_batch* b, const float* dropout_p, uint64_t seed,
                          uint64_t* rng_counter, int32_t training, const void* images,
                          void* arena, float* out, void* stream) {
@@ -683,11 +735,11 @@ static int predict_entry(bool headless, const cgr_gnn_config* cfg, const float* 
   if (rc) return rc;
   rc = validate_batch(cfg, b);
   if (rc) return rc;
+  const bool headless = level != OutLevel::Fused;
   CGR_CHECK(params != nullptr && arena != nullptr && out != nullptr,
-            headless ? "cgr: params / arena / g_out must not be NULL"
-                     : "cgr: params / arena / y must not be NULL");
+            std::string("cgr: params / arena / ") + calls_of(level).out + " must not be NULL");
   CGR_CHECK((training & ~CGR_TRAIN_DROPOUT) == 0,
-            std::string(headless ? "cgr_gnn_encode_predict" : "cgr_gnn_predict") +
+            std::string(calls_of(level).pred) +
                 ": `training` may only hold CGR_TRAIN_DROPOUT (no backward follows)");
   const int np = cgr_gnn_num_params(cfg);
   for (int i = 0; i < np; ++i)
@@ -697,7 +749,7 @@ static int predict_entry(bool headless, const cgr_gnn_config* cfg, const float* 
   FwdMode m;
   m.eval = true;
   m.images = images;
-  m.headless = headless;
+  m.level = level;
   note_forward(arena, -1);  // never a backward's arena
   return gnn_forward_impl(d, params, b, dropout_p, seed, rng_counter, training, arena, out,
                           (hipStream_t)stream, m);
@@ -706,16 +758,24 @@ static int predict_entry(bool headless, const cgr_gnn_config* cfg, const float* 
 int cgr_gnn_predict(const cgr_gnn_config* cfg, const float* const* params, const cgr_batch* b,
                     const float* dropout_p, uint64_t seed, uint64_t* rng_counter,
                     int32_t training, const void* images, void* arena, float* y, void* stream) {
-  return predict_entry(false, cfg, params, b, dropout_p, seed, rng_counter, training, images,
-                       arena, y, stream);
+  return predict_entry(OutLevel::Fused, cfg, params, b, dropout_p, seed, rng_counter, training,
+                       images, arena, y, stream);
 }
 
 int cgr_gnn_encode_predict(const cgr_gnn_config* cfg, const float* const* params,
                            const cgr_batch* b, const float* dropout_p, uint64_t seed,
                            uint64_t* rng_counter, int32_t training, const void* images,
                            void* arena, float* g_out, void* stream) {
-  return predict_entry(true, cfg, params, b, dropout_p, seed, rng_counter, training, images,
-                       arena, g_out, stream);
+  return predict_entry(OutLevel::Pooled, cfg, params, b, dropout_p, seed, rng_counter, training,
+                       images, arena, g_out, stream);
+}
+
+int cgr_gnn_encode_nodes_predict(const cgr_gnn_config* cfg, const float* const* params,
+                                 const cgr_batch* b, const float* dropout_p, uint64_t seed,
+                                 uint64_t* rng_counter, int32_t training, const void* images,
+                                 void* arena, float* n_out, void* stream) {
+  return predict_entry(OutLevel::Nodes, cfg, params, b, dropout_p, seed, rng_counter, training,
+                       images, arena, n_out, stream);
 }
 
 int32_t cgr_device_errors(int32_t device, int32_t clear) {

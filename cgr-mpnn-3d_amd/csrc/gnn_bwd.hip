@@ -69,7 +69,7 @@ struct PendingReduce {
 int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch* b,
                       const float* dropout_p, uint64_t seed, int training, const void* arena,
                       const float* dy, float* const* grads, void* workspace,
-                      hipEvent_t const* bucket_events, hipStream_t st, bool headless) {
+                      hipEvent_t const* bucket_events, hipStream_t st, OutLevel level) {
   const ArenaLayout L = arena_layout(d);
   const IndexView iv = index_view(const_cast<void*>(arena), L);
   const FloatView fv = float_view(const_cast<void*>(arena), L, d);
@@ -193,14 +193,17 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   // then never stored); the fp32 families read dzn
   const WgChoice ro = wgrad_pick(WgSite::Readout, d, x_aligned);
   const bool ro_b3 = ro.family == WgFamily::B3;
-  const bool max_pool = fv.pool_arg != nullptr;  // global_max_pool (CGR_POOL_MAX)
-  // headless (cgr_gnn_encode_backward): `dy` is dg [B, H], a general cotangent of the pooled
-  // embedding -- neither a row nor a column factor, so every pooling mode takes max pooling's
+  // below the fused level (cgr_gnn_encode_backward: `dy` is dg [B, H], a general cotangent of the
+  // pooled embedding; cgr_gnn_encode_nodes_backward: dn [N, H], one of the node embedding) the
+  // upstream is neither a row nor a column factor, so every pooling mode takes max pooling's
   // route: dzn materialised on the main stream before the fork, the NT over the unscaled image;
-  // no head gradients (the ffn entries of params / grads are not touched)
-  const bool dzn_main = max_pool || headless;
+  // no head gradients (the ffn entries of params / grads are not touched).  The nodes level has
+  // no pool at all: the arena's pool_arg region, if cfg.pooling reserved one, was never written
+  const bool fused = level == OutLevel::Fused;
+  const bool max_pool = level != OutLevel::Nodes && fv.pool_arg != nullptr;  // CGR_POOL_MAX
+  const bool dzn_main = max_pool || !fused;
   auto side_readout = [&]() -> int {
-    if (!headless) {  // dwf = dy^T g, dbf: off the main chain (step A/B +0.8 %)
+    if (fused) {  // dwf = dy^T g, dbf: off the main chain (step A/B +0.8 %)
       ProfScope _p("head_bwd", side);
       HIP_RET(head_bwd(dy, fv.g, params[CGR_PARAM_FFN_W(D)], d.B, H, Hp, nullptr,
                        grads[CGR_PARAM_FFN_W(D)], grads[CGR_PARAM_FFN_B(D)], side));
@@ -249,7 +252,11 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   // recorded before it, the side work after -- same dependencies) moves the NT onto the forward's
   // hardware queue in a captured graph but puts the first layer NT beside the readout TN: r05
   // same-box A/B 344.0k -> 341.0k reactions/s (3 runs each, profiles/r05_ro_first_ab.txt)
-  if (headless) {
+  if (level == OutLevel::Nodes) {
+    ProfScope _p("nodes_act_bwd", st);
+    HIP_RET(nodes_act_bwd(dy, fv.hn, fv.zn, N, H, Hp, d.act, dzn, ro_b3 ? img_side : nullptr,
+                          st));
+  } else if (level == OutLevel::Pooled) {
     ProfScope _p("readout_act_bwd_dg", st);
     HIP_RET(readout_act_bwd_dg(dy, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act, dzn,
                                ro_b3 ? img_side : nullptr, st, fv.inv_cnt, fv.pool_arg, fv.g));
@@ -457,7 +464,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
 // into wxT, so both products are one fp32 MFMA NT launch each (gemm.hpp), exact-fp32 products.
 int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* arena,
                          const float* dy, void* workspace, float* dx, float* de, hipStream_t st,
-                         bool headless) {
+                         OutLevel level) {
   const ArenaLayout L = arena_layout(d);
   const IndexView iv = index_view(const_cast<void*>(arena), L);
   const FloatView fv = float_view(const_cast<void*>(arena), L, d);
@@ -482,7 +489,9 @@ int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* 
     {
       ProfScope _p("input_grad_prep", st);
       HIP_RET(segment_sum(dpre0, Hp, iv.src_list, iv.src_ptr, N, H, Gs, Hp, st));
-      if (headless)  // `dy` is dg [B, H] (cgr_gnn_encode_input_grads)
+      if (level == OutLevel::Nodes)  // `dy` is dn [N, H] (cgr_gnn_encode_nodes_input_grads)
+        HIP_RET(nodes_act_bwd(dy, fv.hn, fv.zn, N, H, Hp, d.act, dzn, nullptr, st));
+      else if (level == OutLevel::Pooled)  // `dy` is dg [B, H] (cgr_gnn_encode_input_grads)
         HIP_RET(readout_act_bwd_dg(dy, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act, dzn, nullptr,
                                    st, fv.inv_cnt, fv.pool_arg, fv.g));
       else

@@ -10,7 +10,8 @@
 //                 a_{l+1} = segsum_dst(h_{l+1})                            (GNN.py:90-102, 134)
 //          hn  = act(a_D W_n[:, F:]^T + Q + b_n)   (a_D IS the readout aggregate s, GNN.py:105-107)
 //          y   = (sum_{v in graph} hn[v]) . wf + bf                             (GNN.py:110)
-//          (headless, cgr_gnn_encode: the pooled g [B, H] itself is the output, no head)
+//          (headless, cgr_gnn_encode: the pooled g [B, H] itself is the output, no head;
+//           cgr_gnn_encode_nodes: hn [N, H] itself, no pool either)
 // The reference's discarded readout GEMM (GNN.py:105 -> lin(...) at :141) is not executed.
 #include "dispatch.hpp"
 #include "ep_fwd.hpp"
@@ -180,8 +181,9 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
     if (!mode.eval && (training & CGR_TRAIN_FOR_BACKWARD)) {  // the backward NT GEMMs' W^T images
       B3PackJob rob = b3_job(Wn + F, 1, F + H, H, H, fv.b3rob, rcols);  // scaled by wf: LdActGradT
       // (max pooling: the readout backward NT reads the materialised dzn, wf already in it)
-      // (headless: no wf at all, dzn is materialised from the caller's dg)
-      if (d.pool != CGR_POOL_MAX && !mode.headless) rob.kscale = params[CGR_PARAM_FFN_W(D)];
+      // (below the fused level: no wf at all, dzn is materialised from the caller's dg / dn)
+      if (d.pool != CGR_POOL_MAX && mode.level == OutLevel::Fused)
+        rob.kscale = params[CGR_PARAM_FFN_W(D)];
       HIP_RET(b3_pack_add(pm, rob, st));
       for (int l = 0; l < D; ++l)
         HIP_RET(b3_pack_add(pm, b3_job(params[CGR_PARAM_CONV_W(l)], 1, H, H, H, fv.b3lb[l], lcols),
@@ -345,7 +347,12 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
     HIP_RET(launch_b3nt(LdPlain<4>{fv.a[D], Hp}, static_cast<const b3_u4*>(fv.b3rof), rcols, ep,
                         N, H, H, st, acc));
   }
-  if (mode.headless) {  // y names g_out [B, H]
+  if (mode.level == OutLevel::Nodes) {  // y names n_out [N, H]; no pool, its state untouched
+    ProfScope _p("nodes_out_fwd", st);
+    HIP_RET(nodes_out_fwd(fv.hn, Hp, N, H, y, st));
+    return 0;
+  }
+  if (mode.level == OutLevel::Pooled) {  // y names g_out [B, H]
     ProfScope _p("pool_only_fwd", st);
     HIP_RET(pool_only_fwd(fv.hn, Hp, iv.graph_ptr, d.B, H, fv.g, y, st, fv.inv_cnt, fv.pool_arg,
                           b->batch == nullptr));

@@ -165,13 +165,19 @@ B3Cols image_cols(const Dims& d, int n);
 // the forward weight images are packed into its arena by every call (the weights may have changed
 // by any route: an optimizer writing through raw pointers, a replayed captured step), unless the
 // caller hands pre-packed ones (cgr_gnn_pack_images) and vouches for their freshness.
-// headless (cgr_gnn_encode / _encode_predict): the forward ends in the pool without the ffn
-// head; its `y` argument is the caller's g_out [B, H], and the readout-backward image is packed
-// unscaled for every pooling mode (the headless backward reads a materialised dzn).
+// What a forward hands its caller, and so what cotangent its backward takes.  Fused
+// (cgr_gnn_forward / _predict): y [B], the whole model.  Pooled (cgr_gnn_encode / _encode_predict,
+// "headless"): the forward ends in the pool without the ffn head; its `y` argument is the caller's
+// g_out [B, H].  Nodes (cgr_gnn_encode_nodes / _encode_nodes_predict): it ends after the readout
+// GEMM; `y` is the caller's n_out [N, H], a copy of hn, and nothing of the pooling state (pool_arg,
+// inv_cnt, g) is read or written, whatever d.pool says.  Below Fused there is no wf, so the
+// readout-backward image is packed unscaled for every pooling mode and the backward reads a dzn
+// materialised from the caller's dg [B, H] / dn [N, H].
+enum class OutLevel : int { Fused = 0, Pooled = 1, Nodes = 2 };
 struct FwdMode {
   bool eval = false;
   const void* images = nullptr;
-  bool headless = false;
+  OutLevel level = OutLevel::Fused;
 };
 struct ImageLayout {
   size_t b3x, b3rof, b3lf[CGR_MAX_DEPTH], bytes;

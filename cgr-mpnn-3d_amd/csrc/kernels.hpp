@@ -90,6 +90,15 @@ hipError_t readout_act_bwd_dg(const float* dg, const int* node_graph, const floa
                               void* img, hipStream_t st, const float* gscale = nullptr,
                               const int* pool_arg = nullptr, const float* gpool = nullptr);
 
+// the nodes level (cgr_gnn_encode_nodes*, nodes_kernels.hip): n_out [N, H], row stride H (any
+// 4-byte alignment; nothing outside [N, H] is written), a copy of hn [N, Hp] ...
+hipError_t nodes_out_fwd(const float* hn, int Hp, int64_t N, int H, float* n_out, hipStream_t st);
+// ... and dzn[v, n] = dn[v * H + n] * act'(zn[v, n]) from a cotangent dn [N, H] (fp32, row stride
+// H) of it: fp32 dzn [N, Hp] and / or its e-image (either nullable), pad columns 0; no graph
+// gather, pooling factor or max-pool pick
+hipError_t nodes_act_bwd(const float* dn, const float* hn, const float* zn, int64_t N, int H,
+                         int Hp, int act, float* dzn, void* img, hipStream_t st);
+
 struct LayerBwdArgs {
   // dh_{l+1}: top layer (l == D-1, layer_act_bwd): ds[dst_s[i]]; below (the fused dm GEMM,
   // ep_bwd.hpp): da[dst(i)] - dm[rev_s[i]], da = segsum_src(dm)

@@ -30,8 +30,10 @@ extern "C" {
 #endif
 
 /* ABI 9.  The headless entry points (cgr_gnn_encode, _encode_backward, _encode_input_grads,
- * _encode_predict) were added within ABI 9: they change no existing signature, struct or
- * behaviour, so a binding written against the earlier ABI 9 keeps working. */
+ * _encode_predict) and the nodes-level ones (cgr_gnn_encode_nodes, _encode_nodes_backward,
+ * _encode_nodes_input_grads, _encode_nodes_predict) were added within ABI 9: they change no
+ * existing signature, struct or behaviour, so a binding written against the earlier ABI 9 keeps
+ * working. */
 #define CGR_ABI_VERSION 9
 #define CGR_MAX_DEPTH 32
 
@@ -146,9 +148,12 @@ int64_t cgr_gnn_arena_offset(const cgr_gnn_config* cfg, int64_t num_nodes, int64
  * Hp = round_up(hidden, 4).  Names: "dpre" with `index` = conv layer l (0 .. depth-1): the
  * gradient at layer l's pre-activation; "dpre0": the gradient at the edge init's pre-activation
  * (written in place of the skip sum dh0); "ds": the gradient at the readout aggregate a_D,
- * already divided by the in-degree under mean aggregation (what the top layer gathers at dst).
+ * already divided by the in-degree under mean aggregation (what the top layer gathers at dst);
+ * "dzn_main": the gradient at the readout's pre-activation, node order, pad columns 0 -- valid
+ * only where the backward materialises it in fp32 for the readout GEMM: after
+ * cgr_gnn_encode_backward or cgr_gnn_encode_nodes_backward, and under max pooling.
  * Returns -1 for any other name: buffers that not every dispatch path materialises in fp32
- * (dzn, Gs, dm) are not exposed. */
+ * ("dzn" as such, Gs, dm) are not exposed. */
 int64_t cgr_gnn_workspace_offset(const cgr_gnn_config* cfg, int64_t num_nodes, int64_t num_edges,
                                  int64_t num_graphs, const char* name, int32_t index);
 
@@ -256,6 +261,38 @@ int cgr_gnn_encode_predict(const cgr_gnn_config* cfg, const float* const* params
                            const cgr_batch* batch, const float* dropout_p, uint64_t seed,
                            uint64_t* rng_counter, int32_t training, const void* images,
                            void* arena, float* g_out, void* stream);
+
+/* One level further down: the per-atom embedding hn = act(edge_to_node(cat[x, a_D])), the input
+ * of `self.pooling_fn(h, batch)` (GNN.py:105-108), for atom-level attribution and targets and for
+ * any readout the three native pools cannot express (attention, gated, set2set, a pool over the
+ * reacting atoms only), which then runs on it outside this library.  The four calls mirror the
+ * encode ones argument for argument.  cgr_gnn_encode_nodes is cgr_gnn_forward up to and including
+ * the readout GEMM (same arena layout, dropout keying and counter advance) and writes `n_out`,
+ * device [N, hidden] fp32 with row stride `hidden` (4-byte alignment; nothing outside [N, hidden]
+ * is written).  cgr_gnn_encode_nodes_backward is the reverse mode from a general cotangent `dn`,
+ * device [N, hidden] fp32 with row stride `hidden`, = dLoss/dhn; _encode_nodes_input_grads and
+ * _encode_nodes_predict are the nodes forms of cgr_gnn_input_grads and cgr_gnn_predict.
+ * cfg->pooling takes no part: it still sizes the arena, but no pooling state is read or written.
+ * The ffn.weight / ffn.bias entries of `params` and `grads` may be NULL and are never read or
+ * written.  An arena remembers the level of the forward that filled it -- the fused y, the pooled
+ * g or the nodes -- and every backward / input-gradients entry refuses an arena of another level
+ * (nothing enqueued; cgr_last_error names the call that belongs to the arena). */
+int cgr_gnn_encode_nodes(const cgr_gnn_config* cfg, const float* const* params,
+                         const cgr_batch* batch, const float* dropout_p, uint64_t seed,
+                         uint64_t* rng_counter, int32_t training, void* arena, float* n_out,
+                         void* stream);
+int cgr_gnn_encode_nodes_backward(const cgr_gnn_config* cfg, const float* const* params,
+                                  const cgr_batch* batch, const float* dropout_p, uint64_t seed,
+                                  int32_t training, const void* arena, const float* dn,
+                                  float* const* grads, void* workspace,
+                                  void* const* bucket_events, void* stream);
+int cgr_gnn_encode_nodes_input_grads(const cgr_gnn_config* cfg, const float* const* params,
+                                     const cgr_batch* batch, const void* arena, const float* dn,
+                                     void* workspace, float* dx, float* dedge_attr, void* stream);
+int cgr_gnn_encode_nodes_predict(const cgr_gnn_config* cfg, const float* const* params,
+                                 const cgr_batch* batch, const float* dropout_p, uint64_t seed,
+                                 uint64_t* rng_counter, int32_t training, const void* images,
+                                 void* arena, float* n_out, void* stream);
 
 /* Sticky device-side conditions of `device` (no reference counterpart: the reference's autograd
  * cannot fail this way), read from pinned host memory the kernels write -- no device sync, so a

@@ -152,24 +152,22 @@ hipError_t b3_eimage(const float* x, int64_t ld, int64_t R, int C, b3_u4* img, h
 // e-image of the segmented sum G[v, :C] = sum_{j in [ptr[v], ptr[v+1])} X[idx[j], :C] (the node
 // weight gradient's Gs = segsum_src(dpre0), gnn_bwd.hip) without G ever reaching memory.  Block =
 // one 32-row step s x 64 columns: the sums (thread = (row, float4 column), the segment's rows in
-// order, as k_segsum_v4m adds them) go to an LDS tile [32][65], then thread = (column, 8-row chunk),
-// chunk fastest, splits its 8 values and writes the two 16-byte chunk slots (a wave's stores cover
-// 16 consecutive 64-byte slots).  Rows >= R and columns >= C are written as 0.
-constexpr int kSegImgCols = 64;
+// order, as k_segsum_v4m adds them) go to an LDS tile [32][65], then the tile into the image
+// (b3_tile_to_eimage, gemm_b3tn.hpp).  Rows >= R and columns >= C are written as 0.
 __global__ __launch_bounds__(256) void k_b3_segsum_eimage(const float* __restrict__ x, int64_t ld_,
                                                           const int* __restrict__ idx,
                                                           const int* __restrict__ ptr, int64_t R,
                                                           int C, int cimg,
                                                           b3_u4* __restrict__ img) {
-  __shared__ float tile[32][kSegImgCols + 1];
+  __shared__ float tile[32][kImgCols + 1];
   const int64_t s = blockIdx.y;
-  const int c0 = blockIdx.x * kSegImgCols;
+  const int c0 = blockIdx.x * kImgCols;
   // two (row, float4 column) items per thread (rows r and r + 16), every load of both in flight
   // together: the first three rows of each segment with clamped indices (segments average ~2
   // rows), the rest in a loop -- the runtime-trip-count loop alone serialised idx -> row -> add
   // (10.3 us in the step at cfg2 for 37 MB)
-  static_assert(32 * (kSegImgCols / 4) == 2 * 256, "two items per thread of a 256-thread block");
-  const int r0 = threadIdx.x / (kSegImgCols / 4), c4 = threadIdx.x % (kSegImgCols / 4);
+  static_assert(32 * (kImgCols / 4) == 2 * 256, "two items per thread of a 256-thread block");
+  const int r0 = threadIdx.x / (kImgCols / 4), c4 = threadIdx.x % (kImgCols / 4);
   const int cc = c0 + 4 * c4;
   const bool colok = cc < C;
   int b[2], e[2];
@@ -209,16 +207,7 @@ __global__ __launch_bounds__(256) void k_b3_segsum_eimage(const float* __restric
     for (int k = 0; k < 4; ++k) tile[r0 + 16 * h][4 * c4 + k] = (cc + k < C) ? a[k] : 0.f;
   }
   __syncthreads();
-  const int q = threadIdx.x & 3, cl = threadIdx.x >> 2;  // 64 columns x 4 chunks
-  const int c = c0 + cl;
-  if (c >= cimg) return;
-  float f[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f[j] = tile[8 * q + j][cl];
-  b3_u4 pc[2];
-  b3_split8<2>(f, pc);
-  img[((s * 2 + 0) * cimg + c) * 4 + q] = pc[0];
-  img[((s * 2 + 1) * cimg + c) * 4 + q] = pc[1];
+  b3_tile_to_eimage(tile, s, c0, cimg, img);
 }
 
 hipError_t b3_segsum_eimage(const float* x, int64_t ld, const int* idx, const int* ptr, int64_t R,
@@ -227,50 +216,80 @@ hipError_t b3_segsum_eimage(const float* x, int64_t ld, const int* idx, const in
   const int cimg = b3_eimg_cols(C);
   if (steps <= 0 || C <= 0) return hipSuccess;
   if ((ld & 3) || ld < (C + 3) / 4 * 4 || ((uintptr_t)x & 15)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_b3_segsum_eimage, dim3((cimg + kSegImgCols - 1) / kSegImgCols,
+  hipLaunchKernelGGL(k_b3_segsum_eimage, dim3((cimg + kImgCols - 1) / kImgCols,
                                               (unsigned)steps), dim3(256), 0, st, x, ld, idx, ptr,
                      R, C, cimg, img);
   return hipGetLastError();
 }
 
-
 // ------------------------------------------------------------------------------------------
 // Producers that write the weight-gradient TN's e-image themselves (no k_b3_eimage pass over
 // their output): block = one 32-row step x 64 columns.  Phase 1, thread = (row, float4 column):
 // the element-wise backward of the row, its fp32 result to global (float4 rows, as before) and
-// into an LDS tile; phase 2, thread = (column, 8-row chunk), chunk fastest: the chunk's two
-// bf16 pieces into the image (k_b3_eimage's store pattern).  Rows >= R / columns >= C are 0.
+// into an LDS tile (b3_tile_put); phase 2: the tile into the image (b3_tile_to_eimage,
+// gemm_b3tn.hpp).  Rows >= R / columns >= C are 0.
 // ------------------------------------------------------------------------------------------
-constexpr int kImgCols = 64;
-
-__device__ __forceinline__ void b3_tile_to_eimage(const float (&tile)[32][kImgCols + 1], int64_t s,
-                                                  int c0, int cimg, b3_u4* __restrict__ img) {
-  const int q = threadIdx.x & 3, cl = threadIdx.x >> 2;  // 64 columns x 4 chunks
-  const int c = c0 + cl;
-  if (c >= cimg) return;
-  float f[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f[j] = tile[8 * q + j][cl];
-  b3_u4 pc[2];
-  b3_split8<2>(f, pc);
-  img[((s * 2 + 0) * cimg + c) * 4 + q] = pc[0];
-  img[((s * 2 + 1) * cimg + c) * 4 + q] = pc[1];
+// readout backward (GNN.py:106-110 reversed): dzn[v, n] = up[v, n] act'(zn[v, n]) (ReLU: hn > 0),
+// fp32 dzn (nullable) and / or its e-image (nullable).  What differs between the output levels
+// (kernels.hpp, ReadoutUp) is the upstream value alone: a functor forms the float4 of node v
+// (graph gv), columns n .. n + 3, the per-graph factor gscale (mean pooling, nullable) included,
+// and says in kGraphs whether its level knows graphs (its node_graph, gscale, the max-pool pick).
+// node_graph is a member of the graph levels' functors, not a kernel argument, so the nodes
+// instantiation carries no hole for it in its argument block (one scalar load more otherwise).
+// The operations and their order are pinned bit for bit by tests/test_gpu_encode*.py.
+// fused: dy[graph(v)] wf[n], dg never stored.  The clamp keeps the read inside wf; it leaves the
+// pad columns of the fp32 dzn non-zero (the image's are zeroed by b3_tile_put)
+struct UpFused {
+  static constexpr bool kGraphs = true;
+  const float* __restrict__ dy;  // [B]
+  const float* __restrict__ wf;  // [H]
+  const int* __restrict__ node_graph;
+  __device__ __forceinline__ float4 operator()(int64_t, int gv, int n, int H,
+                                               const float* __restrict__ gscale) const {
+    const float d = gscale ? dy[gv] * gscale[gv] : dy[gv];
+    return make_float4(d * wf[min(n, H - 1)], d * wf[min(n + 1, H - 1)],
+                       d * wf[min(n + 2, H - 1)], d * wf[min(n + 3, H - 1)]);
+  }
+};
+// one row of a cotangent with row stride H (rows of any 4-byte alignment): read element-wise,
+// pad columns n >= H are 0
+__device__ __forceinline__ float4 up_row4(const float* __restrict__ row, int n, int H) {
+  float4 o;
+  o.x = n < H ? row[n] : 0.f;
+  o.y = n + 1 < H ? row[n + 1] : 0.f;
+  o.z = n + 2 < H ? row[n + 2] : 0.f;
+  o.w = n + 3 < H ? row[n + 3] : 0.f;
+  return o;
 }
+// pooled: dg[graph(v), n], a general cotangent of the pooled embedding; a rank-1 dg = dy (x) wf
+// reproduces the fused max-pool bits
+struct UpPooled {
+  static constexpr bool kGraphs = true;
+  const float* __restrict__ dg;  // [B, H]
+  const int* __restrict__ node_graph;
+  __device__ __forceinline__ float4 operator()(int64_t, int gv, int n, int H,
+                                               const float* __restrict__ gscale) const {
+    float4 o = up_row4(dg + (int64_t)gv * H, n, H);
+    if (gscale) {
+      const float gsc = gscale[gv];
+      o = make_float4(o.x * gsc, o.y * gsc, o.z * gsc, o.w * gsc);
+    }
+    return o;
+  }
+};
+// nodes: dn[v, n], a cotangent of the node embedding: no graph gather, factor or pick
+struct UpNodes {
+  static constexpr bool kGraphs = false;
+  const float* __restrict__ dn;  // [N, H]
+  __device__ __forceinline__ float4 operator()(int64_t v, int, int n, int H, const float*) const {
+    return up_row4(dn + v * H, n, H);
+  }
+};
 
-__device__ __forceinline__ void b3_tile_put(float (&tile)[32][kImgCols + 1], int r, int c4,
-                                            int col, int C, const float4& v) {
-  tile[r][4 * c4 + 0] = col + 0 < C ? v.x : 0.f;
-  tile[r][4 * c4 + 1] = col + 1 < C ? v.y : 0.f;
-  tile[r][4 * c4 + 2] = col + 2 < C ? v.z : 0.f;
-  tile[r][4 * c4 + 3] = col + 3 < C ? v.w : 0.f;
-}
-
-// readout backward (GNN.py:106-110 reversed): dzn[v, n] = dy[graph(v)] wf[n] act'(zn[v, n]); dg
-// is never stored.  dzn (nullable) in fp32 and/or its e-image (nullable)
+template <class Up>
 __global__ __launch_bounds__(256) void k_readout_bwd_img(
-    const float* __restrict__ dy, const float* __restrict__ wf, const int* __restrict__ node_graph,
-    const float* __restrict__ hn, const float* __restrict__ zn, int64_t N, int H, int Hp, int act,
-    float* __restrict__ dzn, int colblocks, int cimg, b3_u4* __restrict__ img,
+    Up up, const float* __restrict__ hn, const float* __restrict__ zn, int64_t N, int H, int Hp,
+    int act, float* __restrict__ dzn, int colblocks, int cimg, b3_u4* __restrict__ img,
     const float* __restrict__ gscale, const int* __restrict__ pool_arg,
     const float* __restrict__ gpool) {
   __shared__ float tile[32][kImgCols + 1];
@@ -283,25 +302,24 @@ __global__ __launch_bounds__(256) void k_readout_bwd_img(
     float4 o = f4zero();
     if (v < N && n < Hp) {
       const int64_t off = v * Hp + n;
-      const int gv = node_graph[v];
-      const float d = gscale ? dy[gv] * gscale[gv] : dy[gv];
-      o.x = d * wf[min(n, H - 1)];
-      o.y = d * wf[min(n + 1, H - 1)];
-      o.z = d * wf[min(n + 2, H - 1)];
-      o.w = d * wf[min(n + 3, H - 1)];
-      if (pool_arg) {  // global_max_pool (pool_head_fwd's record, kernels.hpp)
-        const int4 am = *reinterpret_cast<const int4*>(pool_arg + (int64_t)gv * Hp + n);
-        const float4 h = *reinterpret_cast<const float4*>(hn + off);
-        const float4 gm = *reinterpret_cast<const float4*>(gpool + (int64_t)gv * Hp + n);
-        // the first arg-max node (>= 0), or every node holding the max sharing (-count)
-        auto pick = [&](float ov, int a, float hv, float gmv) {
-          if (a >= 0) return a == v ? ov : 0.f;
-          return hv == gmv ? ov / (float)(-a) : 0.f;
-        };
-        o.x = pick(o.x, am.x, h.x, gm.x);
-        o.y = pick(o.y, am.y, h.y, gm.y);
-        o.z = pick(o.z, am.z, h.z, gm.z);
-        o.w = pick(o.w, am.w, h.w, gm.w);
+      int gv = 0;
+      if constexpr (Up::kGraphs) gv = up.node_graph[v];
+      o = up(v, gv, n, H, gscale);
+      if constexpr (Up::kGraphs) {
+        if (pool_arg) {  // global_max_pool (pool_head_fwd's record, kernels.hpp)
+          const int4 am = *reinterpret_cast<const int4*>(pool_arg + (int64_t)gv * Hp + n);
+          const float4 h = *reinterpret_cast<const float4*>(hn + off);
+          const float4 gm = *reinterpret_cast<const float4*>(gpool + (int64_t)gv * Hp + n);
+          // the first arg-max node (>= 0), or every node holding the max sharing (-count)
+          auto pick = [&](float ov, int a, float hv, float gmv) {
+            if (a >= 0) return a == v ? ov : 0.f;
+            return hv == gmv ? ov / (float)(-a) : 0.f;
+          };
+          o.x = pick(o.x, am.x, h.x, gm.x);
+          o.y = pick(o.y, am.y, h.y, gm.y);
+          o.z = pick(o.z, am.z, h.z, gm.z);
+          o.w = pick(o.w, am.w, h.w, gm.w);
+        }
       }
       if (act == ACT_RELU) {
         const float4 h = *reinterpret_cast<const float4*>(hn + off);
@@ -325,16 +343,23 @@ __global__ __launch_bounds__(256) void k_readout_bwd_img(
   b3_tile_to_eimage(tile, s, c0, cimg, img);
 }
 
-hipError_t readout_act_bwd(const float* dy, const float* wf, const int* node_graph,
-                           const float* hn, const float* zn, int64_t N, int H, int Hp, int act,
-                           float* dzn, void* img, hipStream_t st, const float* gscale,
-                           const int* pool_arg, const float* gpool) {
+hipError_t readout_act_bwd(const ReadoutUp& up, const int* node_graph, const float* hn,
+                           const float* zn, int64_t N, int H, int Hp, int act, float* dzn,
+                           void* img, hipStream_t st, const float* gscale, const int* pool_arg,
+                           const float* gpool) {
   if (N <= 0 || (!dzn && !img)) return hipSuccess;
   const int colblocks = (int)cdiv(Hp, kImgCols);
   const int64_t blocks = cdiv(N, 32) * colblocks;
-  hipLaunchKernelGGL(k_readout_bwd_img, dim3((unsigned)blocks), dim3(256), 0, st, dy, wf,
-                     node_graph, hn, zn, N, H, Hp, act, dzn, colblocks, b3_eimg_cols(H),
-                     static_cast<b3_u4*>(img), gscale, pool_arg, gpool);
+  auto launch = [&](auto u, const float* gs, const int* pa, const float* gp) {
+    hipLaunchKernelGGL(k_readout_bwd_img<decltype(u)>, dim3((unsigned)blocks), dim3(256), 0, st,
+                       u, hn, zn, N, H, Hp, act, dzn, colblocks, b3_eimg_cols(H),
+                       static_cast<b3_u4*>(img), gs, pa, gp);
+  };
+  switch (up.level) {
+    case OutLevel::Fused: launch(UpFused{up.up, up.wf, node_graph}, gscale, pool_arg, gpool); break;
+    case OutLevel::Pooled: launch(UpPooled{up.up, node_graph}, gscale, pool_arg, gpool); break;
+    case OutLevel::Nodes: launch(UpNodes{up.up}, nullptr, nullptr, nullptr); break;
+  }
   return hipGetLastError();
 }
 

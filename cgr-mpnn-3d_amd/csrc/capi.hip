@@ -3,10 +3,9 @@
 #include <string.h>
 
 #include <algorithm>
-#include <mutex>
 #include <string>
-#include <unordered_map>
 
+#include "arena_book.hpp"
 #include "dispatch.hpp"
 #include "gnn_internal.hpp"
 #include "kernels.hpp"
@@ -17,40 +16,9 @@ namespace cgr {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 
-// `training` bits of the forward that last filled each arena (host side, so the check costs no
-// device sync and holds under graph capture): the backward needs the W^T images that only a
-// CGR_TRAIN_FOR_BACKWARD forward packs.  Keys are arena addresses; the caching allocator reuses
-// them, so the table stays as small as the set of live arena blocks.
-static std::mutex g_arena_mu;
-static std::unordered_map<const void*, int> g_arena_flags;
-// ... and the precision mode it ran in (enum cgr_precision): the arena's images, counters and
-// saved activations are laid out and filled for that mode, so the backward and the input
-// gradients must be given a config of the same mode
-static std::unordered_map<const void*, int> g_arena_mode;
-// every forward into an arena starts a new generation of it; a backward enqueued on (arena,
-// generation) records its workspace, and cgr_gnn_input_grads -- which reads dpre0 and the
-// readout's operands from that workspace -- requires the record to name the same arena at its
-// current generation (otherwise it silently returned garbage)
-static std::unordered_map<const void*, uint64_t> g_arena_gen;
-static std::unordered_map<const void*, std::pair<const void*, uint64_t>> g_ws_backward;
-// ... and its output level (gnn_internal.hpp: the fused y of cgr_gnn_forward, the pooled g of
-// cgr_gnn_encode, the nodes of cgr_gnn_encode_nodes; below the fused level the readout-backward
-// image is unscaled for every pooling mode, and the nodes level leaves the pooling state
-// unwritten): every backward / input-gradients entry refuses an arena of another level
-static std::unordered_map<const void*, OutLevel> g_arena_level;
-static void note_forward(const void* arena, int flags, int mode = -1,
-                         OutLevel level = OutLevel::Fused) {
-  std::lock_guard<std::mutex> lk(g_arena_mu);
-  g_arena_flags[arena] = flags;
-  g_arena_mode[arena] = mode;
-  g_arena_level[arena] = level;
-  ++g_arena_gen[arena];
-}
-static OutLevel forward_level(const void* arena) {
-  std::lock_guard<std::mutex> lk(g_arena_mu);
-  const auto it = g_arena_level.find(arena);
-  return it == g_arena_level.end() ? OutLevel::Fused : it->second;
-}
+// what the last forward left in each arena, and which workspace holds its backward
+static ArenaBook g_arenas;
+
 // the calls of one output level and the names of its output and cotangent, for the messages
 struct LevelCalls {
   const char *fwd, *bwd, *igr, *pred, *out, *up, *what;
@@ -66,28 +34,6 @@ static const LevelCalls& calls_of(OutLevel level) {
        "per-atom embeddings, no pooling or ffn head"}};
   return k[(int)level];
 }
-static int forward_mode(const void* arena) {
-  std::lock_guard<std::mutex> lk(g_arena_mu);
-  const auto it = g_arena_mode.find(arena);
-  return it == g_arena_mode.end() ? -1 : it->second;
-}
-static int forward_flags(const void* arena) {
-  std::lock_guard<std::mutex> lk(g_arena_mu);
-  const auto it = g_arena_flags.find(arena);
-  return it == g_arena_flags.end() ? -1 : it->second;
-}
-static void note_backward(const void* arena, const void* workspace) {
-  std::lock_guard<std::mutex> lk(g_arena_mu);
-  g_ws_backward[workspace] = {arena, g_arena_gen[arena]};
-}
-static bool backward_matches(const void* arena, const void* workspace) {
-  std::lock_guard<std::mutex> lk(g_arena_mu);
-  const auto it = g_ws_backward.find(workspace);
-  if (it == g_ws_backward.end() || it->second.first != arena) return false;
-  const auto g = g_arena_gen.find(arena);
-  return g != g_arena_gen.end() && g->second == it->second.second;
-}
-
 int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch* b,
                      const float* dropout_p, uint64_t seed, uint64_t* rng_counter, int training,
                      void* arena, float* y, hipStream_t st, const FwdMode& mode);
@@ -530,12 +476,12 @@ static int forward_entry(OutLevel level, const cgr_gnn_config* cfg, const float*
     CGR_CHECK(params[i] != nullptr || (headless && is_ffn_entry(cfg, i)),
               "cgr: NULL parameter pointer");
   const Dims d = make_dims(cfg, b->num_nodes, b->num_edges, b->num_graphs);
-  note_forward(arena, -1);  // not usable by a backward unless the forward below succeeds
+  g_arenas.note_forward(arena, -1);  // not usable by a backward unless the forward below succeeds
   FwdMode m;
   m.level = level;
   const int r = gnn_forward_impl(d, params, b, dropout_p, seed, rng_counter, training, arena, out,
                                  (hipStream_t)stream, m);
-  if (r == 0) note_forward(arena, training, cfg->precision, level);
+  if (r == 0) g_arenas.note_forward(arena, training, cfg->precision, level);
   return r;
 }
 
@@ -581,17 +527,18 @@ static int backward_entry(OutLevel level, const cgr_gnn_config* cfg, const float
                 " / grads / workspace must not be NULL");
   CGR_CHECK((training & ~(CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)) == 0,
             "cgr: unknown `training` bits (CGR_TRAIN_DROPOUT | CGR_TRAIN_FOR_BACKWARD)");
-  const int ff = forward_flags(arena);
+  const ArenaBook::Seen seen = g_arenas.seen(arena, workspace);
+  const int ff = seen.flags;
   CGR_CHECK(ff >= 0 && (ff & CGR_TRAIN_FOR_BACKWARD),
             fn + ": `arena` was not filled by a successful " + fwd + " with "
             "CGR_TRAIN_FOR_BACKWARD set");
-  const LevelCalls& own = calls_of(forward_level(arena));  // the arena's own calls
-  CGR_CHECK(forward_level(arena) == level,
+  const LevelCalls& own = calls_of(seen.level);  // the arena's own calls
+  CGR_CHECK(seen.level == level,
             fn + ": `arena` was filled by " + own.fwd + " (" + own.what + "); its backward is " +
                 own.bwd);
   CGR_CHECK((ff & CGR_TRAIN_DROPOUT) == (training & CGR_TRAIN_DROPOUT),
             fn + ": `training` dropout bit differs from the forward's");
-  CGR_CHECK(forward_mode(arena) == cfg->precision,
+  CGR_CHECK(seen.mode == cfg->precision,
             fn + ": the config's precision differs from the mode `arena`'s forward "
             "ran in");
   const int np = cgr_gnn_num_params(cfg);
@@ -607,7 +554,7 @@ static int backward_entry(OutLevel level, const cgr_gnn_config* cfg, const float
   const int r = gnn_backward_impl(d, params, b, dropout_p, seed, training, arena, up, grads,
                                   workspace, reinterpret_cast<hipEvent_t const*>(bucket_events),
                                   (hipStream_t)stream, level);
-  if (r == 0) note_backward(arena, workspace);
+  if (r == 0) g_arenas.note_backward(arena, workspace);
   return r;
 }
 
@@ -654,18 +601,19 @@ static int input_grads_entry(OutLevel level, const cgr_gnn_config* cfg,
   CGR_CHECK(params != nullptr && arena != nullptr && up != nullptr && workspace != nullptr,
             std::string("cgr: params / arena / ") + calls_of(level).up +
                 " / workspace must not be NULL");
-  const int ff = forward_flags(arena);
+  const ArenaBook::Seen seen = g_arenas.seen(arena, workspace);
+  const int ff = seen.flags;
   CGR_CHECK(ff >= 0 && (ff & CGR_TRAIN_FOR_BACKWARD),
             fn + ": `arena` was not filled by a successful " + fwd + " with "
             "CGR_TRAIN_FOR_BACKWARD set");
-  const LevelCalls& own = calls_of(forward_level(arena));  // the arena's own calls
-  CGR_CHECK(forward_level(arena) == level,
+  const LevelCalls& own = calls_of(seen.level);  // the arena's own calls
+  CGR_CHECK(seen.level == level,
             fn + ": `arena` was filled by " + own.fwd + " (" + own.what +
                 "); its input gradients are " + own.igr);
-  CGR_CHECK(forward_mode(arena) == cfg->precision,
+  CGR_CHECK(seen.mode == cfg->precision,
             fn + ": the config's precision differs from the mode `arena`'s forward "
             "ran in");
-  CGR_CHECK(backward_matches(arena, workspace),
+  CGR_CHECK(seen.backward_here,
             fn + ": `workspace` does not hold a " + bwd + " of this `arena`'s "
             "latest forward (run the backward first, with the same arena and workspace)");
   CGR_CHECK(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dedge_attr & 15) == 0,
@@ -750,7 +698,7 @@ static int predict_entry(OutLevel level, const cgr_gnn_config* cfg, const float*
   m.eval = true;
   m.images = images;
   m.level = level;
-  note_forward(arena, -1);  // never a backward's arena
+  g_arenas.note_forward(arena, -1);  // never a backward's arena
   return gnn_forward_impl(d, params, b, dropout_p, seed, rng_counter, training, arena, out,
                           (hipStream_t)stream, m);
 }

@@ -129,6 +129,37 @@ hipError_t b3_eimage(const float* x, int64_t ld, int64_t R, int C, b3_u4* img, h
 hipError_t b3_segsum_eimage(const float* x, int64_t ld, const int* idx, const int* ptr, int64_t R,
                             int C, b3_u4* img, hipStream_t st);
 
+// The producers that write an e-image themselves (b3_pack.hip: the segmented sum, the readout
+// and the top layer's backward) work in blocks of one 32-row step x kImgCols columns through an
+// LDS tile [32][kImgCols + 1]: b3_tile_put stores one thread's float4 (row r, column group c4,
+// absolute column col; columns >= C as 0), and after a barrier b3_tile_to_eimage, thread =
+// (column, 8-row chunk), chunk fastest, splits its 8 values and writes the chunk's slot in the
+// two piece planes (k_b3_eimage's store pattern: a wave's stores cover 16 consecutive 64-byte
+// slots).  256 threads per block.
+constexpr int kImgCols = 64;
+
+__device__ __forceinline__ void b3_tile_put(float (&tile)[32][kImgCols + 1], int r, int c4,
+                                            int col, int C, const float4& v) {
+  tile[r][4 * c4 + 0] = col + 0 < C ? v.x : 0.f;
+  tile[r][4 * c4 + 1] = col + 1 < C ? v.y : 0.f;
+  tile[r][4 * c4 + 2] = col + 2 < C ? v.z : 0.f;
+  tile[r][4 * c4 + 3] = col + 3 < C ? v.w : 0.f;
+}
+
+__device__ __forceinline__ void b3_tile_to_eimage(const float (&tile)[32][kImgCols + 1], int64_t s,
+                                                  int c0, int cimg, b3_u4* __restrict__ img) {
+  const int q = threadIdx.x & 3, cl = threadIdx.x >> 2;  // 64 columns x 4 chunks
+  const int c = c0 + cl;
+  if (c >= cimg) return;
+  float f[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] = tile[8 * q + j][cl];
+  b3_u4 pc[2];
+  b3_split8<2>(f, pc);
+  img[((s * 2 + 0) * cimg + c) * 4 + q] = pc[0];
+  img[((s * 2 + 1) * cimg + c) * 4 + q] = pc[1];
+}
+
 // Workgroup = CW = 8 compute waves + SW staging waves (warp-specialised: a wave runs one role for
 // the whole kernel, so the registers of the two roles are not live together).
 //   * compute wave w: n-fragments w, w + CW, ... (RN of them, all TNK k-fragments each) plus RX

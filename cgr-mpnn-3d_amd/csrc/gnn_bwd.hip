@@ -202,18 +202,26 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   const bool fused = level == OutLevel::Fused;
   const bool max_pool = level != OutLevel::Nodes && fv.pool_arg != nullptr;  // CGR_POOL_MAX
   const bool dzn_main = max_pool || !fused;
+  // dzn from the level's upstream (`dy` names dy [B], dg [B, H] or dn [N, H]; wf is read at the
+  // fused level only): the TN's e-image, and fp32 where something reads it (the main stream's NT
+  // under dzn_main, an fp32 weight-gradient family)
+  const ReadoutUp up{level, dy, params[CGR_PARAM_FFN_W(D)]};
+  auto form_dzn = [&](hipStream_t s) -> int {
+    ProfScope _p(readout_act_bwd_class(level), s);
+    HIP_RET(readout_act_bwd(up, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act,
+                            dzn_main || !ro_b3 ? dzn : nullptr, ro_b3 ? img_side : nullptr, s,
+                            fv.inv_cnt, fv.pool_arg, fv.g));
+    return 0;
+  };
   auto side_readout = [&]() -> int {
     if (fused) {  // dwf = dy^T g, dbf: off the main chain (step A/B +0.8 %)
       ProfScope _p("head_bwd", side);
       HIP_RET(head_bwd(dy, fv.g, params[CGR_PARAM_FFN_W(D)], d.B, H, Hp, nullptr,
                        grads[CGR_PARAM_FFN_W(D)], grads[CGR_PARAM_FFN_B(D)], side));
     }
-    if (!dzn_main) {  // (max pooling: dzn and its image came from the main stream, below)
-      ProfScope _p("readout_act_bwd", side);
-      HIP_RET(readout_act_bwd(dy, params[CGR_PARAM_FFN_W(D)], iv.node_graph, fv.hn, fv.zn, N, H,
-                              Hp, d.act, ro_b3 ? nullptr : dzn, ro_b3 ? img_side : nullptr,
-                              side, fv.inv_cnt));
-    }
+    // (dzn_main: dzn and its image came from the main stream, below)
+    if (!dzn_main)
+      if (const int rc = form_dzn(side)) return rc;
     // dW_n = dzn^T [x | s], db_n; bucket 0 (edge_to_node, ffn) is complete once its reduction
     // has run.  With x padded to Fp the reduce skips the pad columns.
     return wgrad(WgAt<WgSite::Readout>{}, ro, img_side, dzn, vec_for(xb, ldx, F),
@@ -252,19 +260,8 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   // recorded before it, the side work after -- same dependencies) moves the NT onto the forward's
   // hardware queue in a captured graph but puts the first layer NT beside the readout TN: r05
   // same-box A/B 344.0k -> 341.0k reactions/s (3 runs each, profiles/r05_ro_first_ab.txt)
-  if (level == OutLevel::Nodes) {
-    ProfScope _p("nodes_act_bwd", st);
-    HIP_RET(nodes_act_bwd(dy, fv.hn, fv.zn, N, H, Hp, d.act, dzn, ro_b3 ? img_side : nullptr,
-                          st));
-  } else if (level == OutLevel::Pooled) {
-    ProfScope _p("readout_act_bwd_dg", st);
-    HIP_RET(readout_act_bwd_dg(dy, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act, dzn,
-                               ro_b3 ? img_side : nullptr, st, fv.inv_cnt, fv.pool_arg, fv.g));
-  } else if (max_pool) {  // dzn (fp32 for the NT, and the TN's e-image) before the fork
-    ProfScope _p("readout_act_bwd", st);
-    HIP_RET(readout_act_bwd(dy, params[CGR_PARAM_FFN_W(D)], iv.node_graph, fv.hn, fv.zn, N, H, Hp,
-                            d.act, dzn, ro_b3 ? img_side : nullptr, st, nullptr, fv.pool_arg, fv.g));
-  }
+  if (dzn_main)  // dzn (fp32 for the NT, and the TN's e-image) before the fork
+    if (const int rc = form_dzn(st)) return rc;
   if (side != st) HIP_RET(fork_to(ss, st, side));
   if (const int rc = side_readout()) return rc;
   if (const int rc = readout_nt()) return rc;
@@ -489,14 +486,10 @@ int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* 
     {
       ProfScope _p("input_grad_prep", st);
       HIP_RET(segment_sum(dpre0, Hp, iv.src_list, iv.src_ptr, N, H, Gs, Hp, st));
-      if (level == OutLevel::Nodes)  // `dy` is dn [N, H] (cgr_gnn_encode_nodes_input_grads)
-        HIP_RET(nodes_act_bwd(dy, fv.hn, fv.zn, N, H, Hp, d.act, dzn, nullptr, st));
-      else if (level == OutLevel::Pooled)  // `dy` is dg [B, H] (cgr_gnn_encode_input_grads)
-        HIP_RET(readout_act_bwd_dg(dy, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act, dzn, nullptr,
-                                   st, fv.inv_cnt, fv.pool_arg, fv.g));
-      else
-        HIP_RET(readout_act_bwd(dy, params[CGR_PARAM_FFN_W(D)], iv.node_graph, fv.hn, fv.zn, N, H,
-                                Hp, d.act, dzn, nullptr, st, fv.inv_cnt, fv.pool_arg, fv.g));
+      // `dy` is the level's upstream: dy [B], dg [B, H] or dn [N, H]; wf is read at Fused only
+      const ReadoutUp up{level, dy, params[CGR_PARAM_FFN_W(D)]};
+      HIP_RET(readout_act_bwd(up, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act, dzn, nullptr, st,
+                              fv.inv_cnt, fv.pool_arg, fv.g));
       TransposeJobs tj{};  // wxT [F, ldw] = [W0[:, :F]^T | W_n[:, :F]^T]
       tj.job[0] = TransposeJob{params[CGR_PARAM_EDGE_INIT_W], F + Fe, 0, wxT, ldw, H, F};
       tj.job[1] = TransposeJob{params[CGR_PARAM_E2N_W(D)], F + H, 0, wxT + H, ldw, H, F};

@@ -336,12 +336,18 @@ hipError_t edge_init_segsum_fwd(const float* P, const int* src_s, const float* e
 constexpr int kPoolThreads = 128;
 constexpr int kPoolBatch = 16;
 
+// HEAD: out is y [B], y[b] = g[b].wf + bf.  Without it (the pooled level, cgr_gnn_encode) out is
+// the caller's g_out [B, H] with row stride H: its rows are not 16-byte aligned when H % 4 != 0
+// and a row's last column group must not reach into the next row, so it is stored element by
+// element; wf and bf are not read.  The pool itself -- the summation order over a graph's nodes,
+// the max / first-arg / tie-count record, the inv_cnt scaling, g [B, Hp] -- is the same code.
+template <bool HEAD>
 __global__ __launch_bounds__(kPoolThreads) void k_pool_head(const float* __restrict__ hn, int Hp,
                                                             const int* __restrict__ gptr, int H,
                                                             const float* __restrict__ wf,
                                                             const float* __restrict__ bf,
                                                             float* __restrict__ g,
-                                                            float* __restrict__ y,
+                                                            float* __restrict__ out,
                                                             const float* __restrict__ inv_cnt,
                                                             int* __restrict__ pool_arg,
                                                             bool pool_first) {
@@ -395,17 +401,24 @@ __global__ __launch_bounds__(kPoolThreads) void k_pool_head(const float* __restr
     const float sv[4] = {s.x, s.y, s.z, s.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (n + k < H) dot += sv[k] * wf[n + k];
+      if (n + k < H) {
+        if constexpr (HEAD)
+          dot += sv[k] * wf[n + k];
+        else
+          out[(int64_t)b * H + n + k] = sv[k];
+      }
   }
-  __shared__ float red[kPoolThreads / 64];
-  dot = wave_sum(dot);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dot;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = red[0];
+  if constexpr (HEAD) {
+    __shared__ float red[kPoolThreads / 64];
+    dot = wave_sum(dot);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dot;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float t = red[0];
 #pragma unroll
-    for (int k = 1; k < kPoolThreads / 64; ++k) t += red[k];
-    y[b] = t + bf[0];
+      for (int k = 1; k < kPoolThreads / 64; ++k) t += red[k];
+      out[b] = t + bf[0];
+    }
   }
 }
 
@@ -413,8 +426,50 @@ hipError_t pool_head_fwd(const float* hn, int Hp, const int* gptr, int64_t B, in
                          const float* wf, const float* bf, float* g, float* y, hipStream_t st,
                          const float* inv_cnt, int* pool_arg, bool pool_first) {
   if (B <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pool_head, dim3(B), dim3(kPoolThreads), 0, st, hn, Hp, gptr, H, wf, bf, g,
-                     y, inv_cnt, pool_arg, pool_first);
+  hipLaunchKernelGGL(k_pool_head<true>, dim3(B), dim3(kPoolThreads), 0, st, hn, Hp, gptr, H, wf,
+                     bf, g, y, inv_cnt, pool_arg, pool_first);
+  return hipGetLastError();
+}
+
+hipError_t pool_only_fwd(const float* hn, int Hp, const int* gptr, int64_t B, int H, float* g,
+                         float* g_out, hipStream_t st, const float* inv_cnt, int* pool_arg,
+                         bool pool_first) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pool_head<false>, dim3(B), dim3(kPoolThreads), 0, st, hn, Hp, gptr, H,
+                     nullptr, nullptr, g, g_out, inv_cnt, pool_arg, pool_first);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// the nodes level's output: n_out [N, H] (row stride H) from hn [N, Hp], one thread per float4
+// column group of hn.  n_out's rows are only 4-byte aligned when H % 4 != 0 and a row's last group
+// must not reach into the next row (or past the buffer), so n_out is stored element by element,
+// columns < H only
+// ------------------------------------------------------------------------------------------
+constexpr int kNodesOutThreads = 256;
+
+__global__ __launch_bounds__(kNodesOutThreads) void k_nodes_out(const float* __restrict__ hn,
+                                                                int Hp, int64_t N, int H,
+                                                                float* __restrict__ n_out) {
+  const int C4 = Hp >> 2;
+  const int64_t t = (int64_t)blockIdx.x * kNodesOutThreads + threadIdx.x;
+  if (t >= N * C4) return;
+  const int64_t v = t / C4;
+  const int n = 4 * (int)(t - v * C4);
+  const float4 x = *reinterpret_cast<const float4*>(hn + v * Hp + n);
+  const float xv[4] = {x.x, x.y, x.z, x.w};
+  float* row = n_out + v * H;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (n + k < H) row[n + k] = xv[k];
+}
+
+hipError_t nodes_out_fwd(const float* hn, int Hp, int64_t N, int H, float* n_out,
+                         hipStream_t st) {
+  if (N <= 0) return hipSuccess;
+  const int64_t blocks = cdiv(N * (Hp >> 2), kNodesOutThreads);
+  hipLaunchKernelGGL(k_nodes_out, dim3((unsigned)blocks), dim3(kNodesOutThreads), 0, st, hn, Hp,
+                     N, H, n_out);
   return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "cgr_mpnn3d.h"  // CGR_MAX_DEPTH
+#include "gnn_internal.hpp"  // OutLevel
 
 namespace cgr {
 
@@ -55,11 +56,14 @@ hipError_t pool_head_fwd(const float* hn, int Hp, const int* gptr, int64_t B, in
                          const float* inv_cnt = nullptr, int* pool_arg = nullptr,
                          bool pool_first = false);
 
-// the same pool without the head (cgr_gnn_encode): g as pool_head_fwd writes it (same summation
-// order, record and scaling) and g_out [B, H], row stride H (any alignment); no y
+// the same pool without the head (cgr_gnn_encode; the same kernel body: summation order, record
+// and scaling): g, and g_out [B, H], row stride H (any 4-byte alignment); no y
 hipError_t pool_only_fwd(const float* hn, int Hp, const int* gptr, int64_t B, int H, float* g,
                          float* g_out, hipStream_t st, const float* inv_cnt = nullptr,
                          int* pool_arg = nullptr, bool pool_first = false);
+// the nodes level (cgr_gnn_encode_nodes): n_out [N, H], row stride H (any 4-byte alignment;
+// nothing outside [N, H] is written), a copy of hn [N, Hp]
+hipError_t nodes_out_fwd(const float* hn, int Hp, int64_t N, int H, float* n_out, hipStream_t st);
 
 // mean aggregation / pooling factors: inv_deg[v] = 1 / max(in-degree, 1) from the dst CSR,
 // inv_cnt[b] = 1 / max(nodes of graph b, 1) (either nullable: not computed)
@@ -72,32 +76,28 @@ hipError_t scale_rows(float* a, int Hp, int64_t N, const float* s, hipStream_t s
 hipError_t head_bwd(const float* dy, const float* g, const float* wf, int64_t B, int H, int Hp,
                     float* dg, float* dwf, float* dbf, hipStream_t st);
 
-// dzn[v] = dy[graph(v)] * wf * act'(zn[v])   (ReLU: hn > 0)
+// The upstream cotangent of the readout backward at each output level (OutLevel,
+// gnn_internal.hpp), and the profile class of its launch
+struct ReadoutUp {
+  OutLevel level;
+  const float* up;  // Fused: dy [B]; Pooled: dg [B, H]; Nodes: dn [N, H] (fp32, row stride H)
+  const float* wf;  // Fused: the ffn weight [H]; not read below it
+};
+inline const char* readout_act_bwd_class(OutLevel level) {
+  static const char* const k[3] = {"readout_act_bwd", "readout_act_bwd_dg", "nodes_act_bwd"};
+  return k[(int)level];
+}
+// dzn[v, n] = up[v, n] * act'(zn[v, n])   (ReLU: hn > 0), up[v, n] = dy[graph(v)] * wf[n] (Fused),
+// dg[graph(v), n] (Pooled) or dn[v, n] (Nodes: node_graph, gscale, pool_arg and gpool not read)
 // dzn (may be null: not materialised) and/or its e-image `img` (gemm_b3tn.hpp B3EImg; null: none)
-// gscale (nullable): per-graph factor of dy (mean pooling: inv_cnt); pool_arg (nullable): max
-// pooling (pool_head_fwd's record): dzn[v, n] kept only where v is the column's first arg-max node
-// (entry >= 0) or, for an entry -count, where hn[v, n] equals the pooled g[graph(v), n], divided
-// by count (torch's scatter_reduce amax backward: ties share the gradient)
-hipError_t readout_act_bwd(const float* dy, const float* wf, const int* node_graph,
-                           const float* hn, const float* zn, int64_t N, int H, int Hp, int act,
-                           float* dzn, void* img, hipStream_t st, const float* gscale = nullptr,
+// gscale (nullable): per-graph factor of the upstream (mean pooling: inv_cnt); pool_arg (nullable):
+// max pooling (pool_head_fwd's record): dzn[v, n] kept only where v is the column's first arg-max
+// node (entry >= 0) or, for an entry -count, where hn[v, n] equals the pooled g[graph(v), n],
+// divided by count (torch's scatter_reduce amax backward: ties share the gradient)
+hipError_t readout_act_bwd(const ReadoutUp& up, const int* node_graph, const float* hn,
+                           const float* zn, int64_t N, int H, int Hp, int act, float* dzn,
+                           void* img, hipStream_t st, const float* gscale = nullptr,
                            const int* pool_arg = nullptr, const float* gpool = nullptr);
-// the same from a general cotangent of the pooled embedding (cgr_gnn_encode_backward): the
-// upstream value of dzn[v, n] is dg[graph(v) * H + n] (fp32, row stride H) in place of
-// dy[graph(v)] * wf[n]; gscale, the max-pool pick and the activation follow in the same order
-hipError_t readout_act_bwd_dg(const float* dg, const int* node_graph, const float* hn,
-                              const float* zn, int64_t N, int H, int Hp, int act, float* dzn,
-                              void* img, hipStream_t st, const float* gscale = nullptr,
-                              const int* pool_arg = nullptr, const float* gpool = nullptr);
-
-// the nodes level (cgr_gnn_encode_nodes*, nodes_kernels.hip): n_out [N, H], row stride H (any
-// 4-byte alignment; nothing outside [N, H] is written), a copy of hn [N, Hp] ...
-hipError_t nodes_out_fwd(const float* hn, int Hp, int64_t N, int H, float* n_out, hipStream_t st);
-// ... and dzn[v, n] = dn[v * H + n] * act'(zn[v, n]) from a cotangent dn [N, H] (fp32, row stride
-// H) of it: fp32 dzn [N, Hp] and / or its e-image (either nullable), pad columns 0; no graph
-// gather, pooling factor or max-pool pick
-hipError_t nodes_act_bwd(const float* dn, const float* hn, const float* zn, int64_t N, int H,
-                         int Hp, int act, float* dzn, void* img, hipStream_t st);
 
 struct LayerBwdArgs {
   // dh_{l+1}: top layer (l == D-1, layer_act_bwd): ds[dst_s[i]]; below (the fused dm GEMM,

@@ -67,6 +67,17 @@ class CgrAdamTensor(ctypes.Structure):
     ]
 
 
+class CgrAdamClip(ctypes.Structure):
+    _fields_ = [
+        ("partials", c_void_p),
+        ("num_partials", c_int64),
+        ("grad_norm", c_void_p),
+        ("gate", c_void_p),
+        ("skipped_steps", c_void_p),
+        ("max_norm", c_double),
+    ]
+
+
 # (name, restype, argtypes) of every symbol in include/cgr_mpnn3d.h
 SIGNATURES = [
     ("cgr_abi_version", c_int32, []),
@@ -137,6 +148,12 @@ SIGNATURES = [
     ("cgr_adam_step_lr_ptr", c_int32,
      [POINTER(CgrAdamTensor), c_int32, c_void_p, c_double, c_double, c_double, c_double, c_int32,
       c_int32, c_void_p]),
+    # gradient-norm clipping inside the step (added within ABI 9)
+    ("cgr_grad_sumsq_partials", c_int64, [POINTER(CgrAdamTensor), c_int32]),
+    ("cgr_grad_sumsq", c_int32, [POINTER(CgrAdamTensor), c_int32, c_void_p, c_int64, c_void_p]),
+    ("cgr_adam_step_clip", c_int32,
+     [POINTER(CgrAdamTensor), c_int32, c_double, c_void_p, c_double, c_double, c_double, c_double,
+      c_int32, c_int32, POINTER(CgrAdamClip), c_void_p]),
     ("cgr_collate", c_int32,
      [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
       c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -149,6 +166,14 @@ SIGNATURES = [
      [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     ("cgr_mse_loss_backward", c_int32,
      [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("cgr_l1_loss_forward", c_int32,
+     [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    ("cgr_l1_loss_backward", c_int32,
+     [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("cgr_huber_loss_forward", c_int32,
+     [c_void_p, c_void_p, c_int64, c_int32, c_double, c_void_p, c_void_p]),
+    ("cgr_huber_loss_backward", c_int32,
+     [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
     ("cgr_profile_enable", c_int32, [c_int32]),
     ("cgr_profile_collect", c_int32, []),
     ("cgr_profile_reset", None, []),

@@ -365,6 +365,45 @@ int cgr_adam_step_lr_ptr(const cgr_adam_tensor* tensors, int32_t num_tensors, co
                          double beta1, double beta2, double eps, double weight_decay,
                          int32_t amsgrad, int32_t maximize, void* stream);
 
+/* Global L2 gradient-norm clipping inside the step (added within ABI 9):
+ * torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2.0) followed by the step above,
+ * without the chain of foreach launches and without a host read.  One optimizer step is
+ *   cgr_grad_sumsq once per tensor table (param group), each at its own offset of `partials`;
+ *   cgr_adam_step_clip once per table, the first with num_partials = the sum of the counts.
+ * cgr_grad_sumsq_partials: how many partials cgr_grad_sumsq writes for a table (host only; one per
+ * block of the step kernel's decomposition; grad == NULL and numel <= 0 entries write none).
+ * cgr_grad_sumsq: partials[b] = the fp32 sum of grad^2 over block b, in a fixed order; float4
+ * loads where the gradient pointer is 16-byte aligned, scalar otherwise.  `capacity` is the
+ * number of floats behind `partials`; a table that needs more is an error before any launch. */
+int64_t cgr_grad_sumsq_partials(const cgr_adam_tensor* tensors, int32_t num_tensors);
+int cgr_grad_sumsq(const cgr_adam_tensor* tensors, int32_t num_tensors, float* partials,
+                   int64_t capacity, void* stream);
+/* The step with the gradient scaled in registers by coef = min(1, max_norm / (norm + 1e-6))
+ * before maximize and weight_decay apply (p.grad itself is not written: torch scales it in
+ * place).  All pointers are device memory owned by the caller and static across steps:
+ *   partials, num_partials: num_partials > 0 makes this call finalise the step's norm before its
+ *     update: the step-count kernel sums the partials in a fixed order in double (no float
+ *     atomics: identical gradient bits give identical norm bits), writes *grad_norm =
+ *     (float)sqrt(sum), sets *gate = 1 if the sum is not finite (or the unpaired-backward timeout
+ *     is flagged, as in cgr_adam_step), else 0, and adds 1 to *skipped_steps for a non-finite
+ *     sum.  num_partials == 0: an earlier call of the same step did, and this one reads them.
+ *   *gate != 0 skips the update: parameters, moments and *step stay as they were.
+ *   max_norm: > 0 (infinity allowed: measured, never clipped); <= 0 = this table is not scaled,
+ *     but still gated.
+ *   lr_dev: NULL = the host value `lr`; else the device scalar of cgr_adam_step_lr_ptr. */
+typedef struct cgr_adam_clip {
+  const float* partials;
+  int64_t num_partials;
+  float* grad_norm;
+  int32_t* gate;
+  int64_t* skipped_steps;
+  double max_norm;
+} cgr_adam_clip;
+int cgr_adam_step_clip(const cgr_adam_tensor* tensors, int32_t num_tensors, double lr,
+                       const float* lr_dev, double beta1, double beta2, double eps,
+                       double weight_decay, int32_t amsgrad, int32_t maximize,
+                       const cgr_adam_clip* clip, void* stream);
+
 /* On-device collation (replaces torch_geometric.loader.DataLoader / Batch.from_data_list in
  * trainer.py:105-118 over the per-reaction Data of ChemDataset.py:81-94).  The store holds every
  * graph of a dataset collated once on the device: graph g owns node rows [node_ptr[g],
@@ -422,6 +461,23 @@ int cgr_mse_loss_forward(const float* input, const float* target, int64_t n,
 int cgr_mse_loss_backward(const float* input, const float* target, const float* grad_loss,
                           int64_t n, int32_t reduction_mean, float* grad_input,
                           float* grad_target, void* stream);
+/* The robust losses beside it (added within ABI 9), argument for argument the MSE pair, with
+ * d = input - target:
+ *   torch.nn.L1Loss: sum |d| (/ n); grad_input = sign(d) grad_loss[0] (/ n), 0 at d == 0.
+ *   torch.nn.HuberLoss(delta), delta > 0: sum of d^2 / 2 where |d| < delta, else
+ *     delta (|d| - delta / 2) (/ n); grad_input = d grad_loss[0] (/ n) where |d| <= delta, else
+ *     delta sign(d) grad_loss[0] (/ n).
+ * grad_target = -grad_input.  One launch each, deterministic. */
+int cgr_l1_loss_forward(const float* input, const float* target, int64_t n,
+                        int32_t reduction_mean, float* loss, void* stream);
+int cgr_l1_loss_backward(const float* input, const float* target, const float* grad_loss,
+                         int64_t n, int32_t reduction_mean, float* grad_input,
+                         float* grad_target, void* stream);
+int cgr_huber_loss_forward(const float* input, const float* target, int64_t n,
+                           int32_t reduction_mean, double delta, float* loss, void* stream);
+int cgr_huber_loss_backward(const float* input, const float* target, const float* grad_loss,
+                            int64_t n, int32_t reduction_mean, double delta, float* grad_input,
+                            float* grad_target, void* stream);
 
 /* Instrumentation (no reference counterpart): per-kernel-class device time measured with HIP
  * events recorded on the launch stream around every launch of cgr_gnn_forward/_backward.

@@ -125,7 +125,19 @@ const char* cgr_last_error(void);
 int cgr_gnn_num_params(const cgr_gnn_config* cfg);
 
 /* Bytes of the per-forward arena (index bookkeeping + activations saved for backward) and of the
- * backward scratch workspace.  The caller owns both (e.g. torch.empty(uint8) on the device). */
+ * backward scratch workspace.  The caller owns both (e.g. torch.empty(uint8) on the device).
+ *
+ * The contract of every caller-owned buffer of the GNN entry points -- this arena and workspace,
+ * the predict arena (cgr_gnn_predict_arena_bytes), the images of cgr_gnn_pack_images
+ * (cgr_gnn_image_bytes), the gradient table's tensors, dx / dedge_attr and the outputs:
+ *   - its contents on entry are arbitrary (another batch's arena, NaNs, anything): no result
+ *     depends on them, the library writes whatever it later reads;
+ *   - nothing outside the reported bytes (the size queries; the shapes of the outputs) is written;
+ *   - the pad columns of the saved buffers (columns hidden .. Hp - 1 of the rows behind
+ *     cgr_gnn_arena_offset / cgr_gnn_workspace_offset) are unspecified unless a buffer's
+ *     description says otherwise; the bytes between a named region's end and the next region's
+ *     256-byte-aligned start are left as they were.
+ * tests/test_gpu_arena_contract.py holds every entry point to it. */
 int64_t cgr_gnn_arena_bytes(const cgr_gnn_config* cfg, int64_t num_nodes, int64_t num_edges,
                             int64_t num_graphs);
 int64_t cgr_gnn_workspace_bytes(const cgr_gnn_config* cfg, int64_t num_nodes, int64_t num_edges,

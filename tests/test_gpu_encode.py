@@ -22,6 +22,7 @@ import pytest
 import torch
 import torch.nn as nn
 
+from arena_contract_common import guarded_run_buffers
 from conftest import golden_cases, load_golden
 from encode_common import encode_backward, encode_forward, general_dg, ragged_batch
 from stagewise_common import TORCH_F32, failures, mixed_dy, param_names, write_report
@@ -347,15 +348,33 @@ def test_encode_stages_against_float64(name, cuda_device):
     lib = native.load()
     lib.cgr_profile_reset()
     lib.cgr_profile_enable(1)
-    try:
-        enc = c.run(True)
-        grads = enc.backward(dg, params)
-        dx, _ = enc.input_grads(dg, params, enc.ws)
+    def once(fill):
+        # arena, workspace and gradient buffer: guarded caller buffers that start from `fill`
+        # (arena_contract_common.py; "ones": every float NaN, every int -1)
+        bufs, gviews = guarded_run_buffers(c.cfg, N, E, c.B, params, fill, cuda_device)
+        run = c.run(True, arena=bufs["arena"].payload)
+        gr = run.backward(dg, params, ws=bufs["ws"].payload, grads=gviews)
+        gx, _ = run.input_grads(dg, params, run.ws)
         torch.cuda.synchronize()
+        for k, g in bufs.items():
+            g.check_guards(k)
+        return run, gr, gx
+
+    try:
+        enc, grads, dx = once("ones")  # the run judged against float64 starts from NaN
     finally:
         lib.cgr_profile_enable(0)
     classes = set(native.profile_report())
     lib.cgr_profile_reset()
+    enc2, grads2, dx2 = once("zero")  # ... and equals, bit for bit, the one that starts from 0
+    same = [("g_out", enc.g_out, enc2.g_out), ("dx", dx, dx2)]
+    same += [(k, a, b) for k, a, b in zip(c.names, grads, grads2) if a is not None]
+    same += [(k, enc.floats(k, n), enc2.floats(k, n)) for k, n in (("hn", N), ("g", c.B))]
+    same += [(k, enc.ws_floats(k, n), enc2.ws_floats(k, n))
+             for k, n in (("ds", N), ("dpre0", E), ("dzn_main", N))]
+    for k, a, b in same:
+        assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes(), \
+            f"{name}: {k} depends on the fill"
     assert {"pool_only_fwd", "readout_act_bwd_dg"} <= classes and "head_bwd" not in classes
     forms = [f for f in ("", "[tnr]", "[f32]") if READOUT_TN + f in classes]
     assert len(forms) == 1 and (forms[0] == "") == (family == "b3"), sorted(classes)

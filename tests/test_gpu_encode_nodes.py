@@ -20,6 +20,7 @@ import pytest
 import torch
 import torch.nn as nn
 
+from arena_contract_common import guarded_run_buffers
 from conftest import golden_cases, load_golden
 from encode_common import general_dg
 from nodes_common import nodes_backward, nodes_forward
@@ -218,14 +219,32 @@ def test_dzn_stage_against_float64(act, H, cuda_device):
     lib = native.load()
     lib.cgr_profile_reset()
     lib.cgr_profile_enable(1)
-    try:
-        run = c.run_nodes()
-        run.backward(dn, params)
+    def once(fill):
+        # arena, workspace and gradient buffer: guarded caller buffers that start from `fill`
+        # (arena_contract_common.py; "ones": every float NaN, every int -1)
+        E = c.b.edge_index.shape[1]
+        bufs, gviews = guarded_run_buffers(c.cfg, N, E, c.B, params, fill, cuda_device)
+        r = c.run_nodes(arena=bufs["arena"].payload)
+        gr = r.backward(dn, params, ws=bufs["ws"].payload, grads=gviews)
         torch.cuda.synchronize()
+        for k, g in bufs.items():
+            g.check_guards(k)
+        return r, gr
+
+    try:
+        run, grads = once("ones")  # the run judged against float64 starts from NaN
     finally:
         lib.cgr_profile_enable(0)
     classes = set(native.profile_report())
     lib.cgr_profile_reset()
+    run2, grads2 = once("zero")  # ... and equals, bit for bit, the one that starts from 0
+    same = [("n_out", run.n_out, run2.n_out), ("hn", run.floats("hn", N), run2.floats("hn", N)),
+            ("dzn_main", run.ws_floats_padded("dzn_main", N),
+             run2.ws_floats_padded("dzn_main", N)),
+            ("ds", run.ws_floats("ds", N), run2.ws_floats("ds", N))]
+    same += [(k, a, b) for k, a, b in zip(c.names, grads, grads2) if a is not None]
+    for k, a, b in same:
+        assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes(), f"{k} depends on the fill"
     assert {"nodes_out_fwd", "nodes_act_bwd"} <= classes, sorted(classes)
     assert not {"pool_only_fwd", "pool_head_fwd", "head_bwd", "readout_act_bwd_dg",
                 "readout_act_bwd"} & classes, sorted(classes)

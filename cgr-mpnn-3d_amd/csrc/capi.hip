@@ -37,8 +37,8 @@ static const LevelCalls& calls_of(OutLevel level) {
 int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch* b,
                      const float* dropout_p, uint64_t seed, uint64_t* rng_counter, int training,
                      void* arena, float* y, hipStream_t st, const FwdMode& mode);
-hipError_t pack_forward_images(const Dims& d, const float* const* params, const ImageLayout& IL,
-                               void* images, hipStream_t st);
+hipError_t pack_forward_images(const Dims& d, const float* const* params, const Images& im,
+                               hipStream_t st);
 int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch* b,
                       const float* dropout_p, uint64_t seed, int training, const void* arena,
                       const float* dy, float* const* grads, void* workspace,
@@ -67,191 +67,137 @@ Dims make_dims(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B) {
   return d;
 }
 
-int bwd_seg_tiles(const Dims& d);
+// ---- layouts: each function below states every region of one buffer once, in placement order,
+// as a call on the placer (layout.hpp); the views, the byte totals and the offset queries all
+// come from these statements.  A new region is a member of its view (gnn_internal.hpp) and one
+// line here.
 
-namespace {
-struct Bump {
-  size_t off = 0;
-  size_t take(size_t bytes) {
-    const size_t o = off;
-    off = (size_t)round_up((int64_t)(off + bytes), (int64_t)kAlign);
-    return o;
+// The forward weight images in the column tilings given: one sizing rule for the training arena
+// (which places each backward image behind its forward one: `bwd`), the eval arena and a
+// caller-packed image buffer
+template <class V>
+static void image_regions(const Dims& d, const B3Cols& cx, const B3Cols& cr, const B3Cols& cl,
+                          bool bwd, Images& im, V& v) {
+  v(im.b3x, 16 * b3_img_u4(cx, d.F), d.F > 0);
+  v(im.b3rof, 16 * b3_img_u4(cr, d.H));
+  v(im.b3rob, 16 * b3_img_u4(cr, d.H), bwd);
+  for (int l = 0; l < d.D; ++l) {
+    v(im.b3lf[l], 16 * b3_img_u4(cl, d.H));
+    v(im.b3lb[l], 16 * b3_img_u4(cl, d.H), bwd);
   }
-};
-constexpr size_t kNone = (size_t)-1;
-}  // namespace
+}
 
-// index bookkeeping, sorted edge features and the x-GEMM outputs: shared by both layouts
-static void layout_prefix(const Dims& d, ArenaLayout& L, Bump& b) {
+// index bookkeeping, sorted edge features and the x-GEMM outputs: the prefix both arenas share
+// (a predict arena's `status` is read at the training layout's offset)
+template <class V>
+static void prefix_regions(const Dims& d, ArenaView& a, V& v) {
+  IndexView& i = a.idx;
+  FloatView& f = a.flt;
   const size_t N = (size_t)d.N, E = (size_t)d.E, B = (size_t)d.B, Hp = (size_t)d.Hp;
-  // zero block: six int arrays back to back, padded to a multiple of 16 bytes
-  L.zero_block = b.off;
-  L.deg_dst = b.off;
-  L.deg_src = L.deg_dst + 4 * N;
-  L.cursor = L.deg_src + 4 * N;
-  L.cursor2 = L.cursor + 4 * N;
-  L.graph_cnt = L.cursor2 + 4 * N;
-  L.status = L.graph_cnt + 4 * B;
-  // + the ticket counters of the layer GEMMs' hub segments (EpLayerSeg, ep_fwd.hpp: zero on entry, reset by
-  // each completer)
-  L.fcnt = L.status + 16;
   // the layer forward runs in layer_cols(d), or in image_cols(d, H) over caller-packed images
   // (predict)
   const B3Cols lc = layer_cols(d), dc = image_cols(d, d.H);
-  const size_t fcnt_n = N * (size_t)std::max(lc.tiles, dc.tiles);
-  L.zero_bytes = (size_t)round_up((int64_t)(4 * (4 * N + B) + 16 + 4 * fcnt_n), 16);
-  b.take(L.zero_bytes);
-  L.rng = b.take(8);
-  L.perm = b.take(4 * E);
-  L.src_s = b.take(4 * E);
-  L.dst_s = b.take(4 * E);
-  L.rev_s = b.take(4 * E);
-  L.src_list = b.take(4 * E);
-  L.inv = b.take(4 * E);
-  L.src_c = b.take(4 * E);
-  L.dst_c = b.take(4 * E);
-  L.dst_ptr = b.take(4 * (N + 1));
-  L.src_ptr = b.take(4 * (N + 1));
-  L.graph_ptr = b.take(4 * (B + 1));
-  L.node_graph = b.take(4 * N);
-  L.e_s = d.Fep ? b.take(4 * E * (size_t)d.Fep) : kNone;
-  L.w0eT = d.Fe ? b.take(4 * (size_t)d.Fe * Hp) : kNone;
-  L.P = b.take(4 * N * Hp);
-  L.Q = b.take(4 * N * Hp);
-  L.xp = (d.F % 4 != 0) ? b.take(4 * N * (size_t)d.Fp) : kNone;
-  L.inv_deg = d.aggr == CGR_AGGR_MEAN ? b.take(4 * N) : kNone;
-  L.inv_cnt = d.pool == CGR_POOL_MEAN ? b.take(4 * B) : kNone;
-  L.pool_arg = d.pool == CGR_POOL_MAX ? b.take(4 * B * Hp) : kNone;
+  // zero block: six int arrays back to back + the ticket counters of the layer GEMMs' hub
+  // segments (EpLayerSeg, ep_fwd.hpp: zero on entry, reset by each completer), padded to a
+  // multiple of 16 bytes
+  v.packed(i.deg_dst, N);
+  v.packed(i.deg_src, N);
+  v.packed(i.cursor, N);
+  v.packed(i.cursor2, N);
+  v.packed(i.graph_cnt, B);
+  v.packed(i.status, 4, "status");
+  v.packed(i.fcnt, N * (size_t)std::max(lc.tiles, dc.tiles));
+  v.block(i.zero_block, i.deg_dst, 16);
+  v("rng", i.rng, 1);
+  v("perm", i.perm, E);
+  v("src_s", i.src_s, E);
+  v("dst_s", i.dst_s, E);
+  v("rev_s", i.rev_s, E);
+  v("src_list", i.src_list, E);
+  v(i.inv, E);
+  v(i.src_c, E);
+  v(i.dst_c, E);
+  v("dst_ptr", i.dst_ptr, N + 1);
+  v("src_ptr", i.src_ptr, N + 1);
+  v("graph_ptr", i.graph_ptr, B + 1);
+  v("node_graph", i.node_graph, N);
+  v("e_s", f.e_s, E * (size_t)d.Fep, d.Fep != 0);
+  v(f.w0eT, (size_t)d.Fe * Hp, d.Fe != 0);
+  v("P", f.P, N * Hp);
+  v("Q", f.Q, N * Hp);
+  v(f.xp, N * (size_t)d.Fp, d.F % 4 != 0);
+  v(f.inv_deg, N, d.aggr == CGR_AGGR_MEAN);
+  v(f.inv_cnt, B, d.pool == CGR_POOL_MEAN);
+  v(f.pool_arg, B * Hp, d.pool == CGR_POOL_MAX);
   // partial sums of the layer GEMMs' hub segments (over >= 3 row tiles), one slot pair per tile
   const size_t rt = (size_t)cdiv(d.E, b3nt_rows((int)d.E, d.H));
-  L.fpart = b.take(4 * rt * 2 * 16 *
-                   std::max((size_t)lc.tiles * lc.nf, (size_t)dc.tiles * dc.nf));
+  v(f.fpart, rt * 2 * 16 * std::max((size_t)lc.tiles * lc.nf, (size_t)dc.tiles * dc.nf));
 }
 
-ArenaLayout arena_layout(const Dims& d) {
-  ArenaLayout L;
-  memset(&L, 0xff, sizeof(L));
-  Bump b;
+// training arena (cgr_gnn_forward and its kin): every activation the backward reads is saved
+template <class V>
+static size_t train_regions(const Dims& d, ArenaView& a, V& v) {
+  FloatView& f = a.flt;
   const size_t N = (size_t)d.N, E = (size_t)d.E, B = (size_t)d.B, Hp = (size_t)d.Hp;
-  layout_prefix(d, L, b);
-  L.b3x = d.F > 0 ? b.take(16 * b3_img_u4(x_cols(d), d.F)) : kNone;
-  // the node-row readout GEMMs in their grid-filling column tiling (readout_cols)
-  const B3Cols rc = readout_cols(d);
-  L.b3rof = b.take(16 * b3_img_u4(rc, d.H));
-  L.b3rob = b.take(16 * b3_img_u4(rc, d.H));
-  for (int l = 0; l < d.D; ++l) {
-    L.b3lf[l] = b.take(16 * b3_img_u4(layer_cols(d), d.H));
-    L.b3lb[l] = b.take(16 * b3_img_u4(layer_cols(d), d.H));
+  prefix_regions(d, a, v);
+  // the x-GEMM and the node-row readout GEMMs in their grid-filling column tilings
+  image_regions(d, x_cols(d), readout_cols(d), layer_cols(d), true, f, v);
+  for (int l = 0; l <= d.D; ++l) {
+    v("h", f.h[l], E * Hp, true, l);
+    v("a", f.a[l], N * Hp, true, l);
+    v("pre", f.pre[l], E * Hp, d.act != CGR_ACT_RELU, l);
   }
-  for (int l = 0; l <= CGR_MAX_DEPTH; ++l) {
-    L.h[l] = l <= d.D ? b.take(4 * E * Hp) : kNone;
-    L.a[l] = l <= d.D ? b.take(4 * N * Hp) : kNone;
-    L.pre[l] = (l <= d.D && d.act != CGR_ACT_RELU) ? b.take(4 * E * Hp) : kNone;
-  }
-  L.zn = d.act != CGR_ACT_RELU ? b.take(4 * N * Hp) : kNone;
-  L.hn = b.take(4 * N * Hp);
-  L.g = b.take(4 * B * Hp);
-  L.bytes = b.off;
-  L.off_index_begin = 0;
-  return L;
+  v("zn", f.zn, N * Hp, d.act != CGR_ACT_RELU);
+  v("hn", f.hn, N * Hp);
+  v("g", f.g, B * Hp);
+  return v.off;
 }
 
-ArenaLayout eval_arena_layout(const Dims& d) {
-  ArenaLayout L;
-  memset(&L, 0xff, sizeof(L));
-  Bump b;
+// eval arena (cgr_gnn_predict and its kin): h_1 .. h_D alias a two-buffer ring, a_0 .. a_D a
+// three-buffer ring; the forward images are packed into it by every predict that is not handed
+// pre-packed ones
+template <class V>
+static size_t eval_regions(const Dims& d, ArenaView& a, V& v) {
+  FloatView& f = a.flt;
   const size_t N = (size_t)d.N, E = (size_t)d.E, B = (size_t)d.B, Hp = (size_t)d.Hp;
-  layout_prefix(d, L, b);
-  const size_t h0 = b.take(4 * E * Hp);
-  const size_t hr[2] = {d.D >= 2 ? b.take(4 * E * Hp) : kNone, b.take(4 * E * Hp)};
-  const size_t ar[3] = {b.take(4 * N * Hp), b.take(4 * N * Hp),
-                        d.D >= 2 ? b.take(4 * N * Hp) : kNone};
-  for (int l = 0; l <= CGR_MAX_DEPTH; ++l) {
-    L.h[l] = l > d.D ? kNone : (l == 0 ? h0 : hr[l & 1]);
-    L.a[l] = l > d.D ? kNone : ar[l % 3];
+  prefix_regions(d, a, v);
+  Reg<float> hr[2], ar[3];
+  v(f.h[0], E * Hp);
+  v(hr[0], E * Hp, d.D >= 2);
+  v(hr[1], E * Hp);
+  v(ar[0], N * Hp);
+  v(ar[1], N * Hp);
+  v(ar[2], N * Hp, d.D >= 2);
+  for (int l = 0; l <= d.D; ++l) {
+    if (l > 0) f.h[l] = hr[l & 1];
+    f.a[l] = ar[l % 3];
   }
-  L.hn = b.take(4 * N * Hp);
-  L.g = b.take(4 * B * Hp);
-  // forward weight images, packed by every predict that is not handed pre-packed ones
-  L.b3x = d.F > 0 ? b.take(16 * b3_img_u4(x_cols(d), d.F)) : kNone;
-  L.b3rof = b.take(16 * b3_img_u4(readout_cols(d), d.H));
-  for (int l = 0; l < d.D; ++l) L.b3lf[l] = b.take(16 * b3_img_u4(layer_cols(d), d.H));
-  L.bytes = b.off;
-  L.off_index_begin = 0;
-  return L;
+  v(f.hn, N * Hp);
+  v(f.g, B * Hp);
+  image_regions(d, x_cols(d), readout_cols(d), layer_cols(d), false, f, v);
+  return v.off;
 }
 
-ImageLayout image_layout(const Dims& d) {
-  ImageLayout I;
-  Bump b;
-  const B3Cols cx = image_cols(d, 2 * d.H), ch = image_cols(d, d.H);
-  I.b3x = d.F > 0 ? b.take(16 * b3_img_u4(cx, d.F)) : kNone;
-  I.b3rof = b.take(16 * b3_img_u4(ch, d.H));
-  for (int l = 0; l < CGR_MAX_DEPTH; ++l) I.b3lf[l] = l < d.D ? b.take(16 * b3_img_u4(ch, d.H)) : kNone;
-  I.bytes = b.off;
-  return I;
+// caller-packed image buffer (cgr_gnn_pack_images): batch-independent tilings
+template <class V>
+static size_t image_buffer_regions(const Dims& d, Images& im, V& v) {
+  image_regions(d, image_cols(d, 2 * d.H), image_cols(d, d.H), image_cols(d, d.H), false, im, v);
+  return v.off;
 }
 
-static inline void* at(void* base, size_t off) {
-  return off == kNone ? nullptr : static_cast<char*>(base) + off;
+ArenaView arena_view(const Dims& d, bool eval, void* arena) {
+  ArenaView a;
+  Placer<> v{static_cast<char*>(arena)};
+  eval ? eval_regions(d, a, v) : train_regions(d, a, v);
+  return a;
 }
 
-IndexView index_view(void* arena, const ArenaLayout& L) {
-  IndexView v;
-  v.deg_dst = (int*)at(arena, L.deg_dst);
-  v.deg_src = (int*)at(arena, L.deg_src);
-  v.cursor = (int*)at(arena, L.cursor);
-  v.cursor2 = (int*)at(arena, L.cursor2);
-  v.graph_cnt = (int*)at(arena, L.graph_cnt);
-  v.status = (int*)at(arena, L.status);
-  v.fcnt = (int*)at(arena, L.fcnt);
-  v.fpart = (float*)at(arena, L.fpart);
-  v.rng = (uint64_t*)at(arena, L.rng);
-  v.zero_block = at(arena, L.zero_block);
-  v.zero_bytes = L.zero_bytes;
-  v.perm = (int*)at(arena, L.perm);
-  v.src_s = (int*)at(arena, L.src_s);
-  v.dst_s = (int*)at(arena, L.dst_s);
-  v.rev_s = (int*)at(arena, L.rev_s);
-  v.src_list = (int*)at(arena, L.src_list);
-  v.inv = (int*)at(arena, L.inv);
-  v.src_c = (int*)at(arena, L.src_c);
-  v.dst_c = (int*)at(arena, L.dst_c);
-  v.dst_ptr = (int*)at(arena, L.dst_ptr);
-  v.src_ptr = (int*)at(arena, L.src_ptr);
-  v.graph_ptr = (int*)at(arena, L.graph_ptr);
-  v.node_graph = (int*)at(arena, L.node_graph);
-  return v;
+Images image_view(const Dims& d, void* images) {
+  Images im;
+  Placer<> v{static_cast<char*>(images)};
+  image_buffer_regions(d, im, v);
+  return im;
 }
-
-FloatView float_view(void* arena, const ArenaLayout& L, const Dims& d) {
-  FloatView f;
-  f.e_s = (float*)at(arena, L.e_s);
-  f.w0eT = (float*)at(arena, L.w0eT);
-  f.P = (float*)at(arena, L.P);
-  f.Q = (float*)at(arena, L.Q);
-  f.xp = (float*)at(arena, L.xp);
-  f.inv_deg = (float*)at(arena, L.inv_deg);
-  f.inv_cnt = (float*)at(arena, L.inv_cnt);
-  f.pool_arg = (int*)at(arena, L.pool_arg);
-  for (int l = 0; l <= CGR_MAX_DEPTH; ++l) {
-    f.h[l] = (float*)at(arena, L.h[l]);
-    f.a[l] = (float*)at(arena, L.a[l]);
-    f.pre[l] = (float*)at(arena, L.pre[l]);
-  }
-  f.zn = (float*)at(arena, L.zn);
-  f.hn = (float*)at(arena, L.hn);
-  f.g = (float*)at(arena, L.g);
-  f.b3x = at(arena, L.b3x);
-  f.b3rof = at(arena, L.b3rof);
-  f.b3rob = at(arena, L.b3rob);
-  for (int l = 0; l < CGR_MAX_DEPTH; ++l) {
-    f.b3lf[l] = l < d.D ? at(arena, L.b3lf[l]) : nullptr;
-    f.b3lb[l] = l < d.D ? at(arena, L.b3lb[l]) : nullptr;
-  }
-  return f;
-}
-
 // column tiling of the layer GEMMs (forward and fused backward) over this batch's E rows: b3_cols
 // when that fills the chip, else the narrower tiles of b3nt_cols (small batches: train.py's 32
 // reactions run 60 -> 210 workgroups per layer GEMM)
@@ -276,56 +222,66 @@ int bwd_dsig_slots(const Dims& d) {
   return (int)std::max<int64_t>(2 * (int64_t)bwd_seg_tiles(d), layer_act_bwd_blocks(d.E, d.Hp));
 }
 
-WorkspaceLayout workspace_layout(const Dims& d) {
-  WorkspaceLayout W;
-  Bump b;
+// backward workspace (cgr_gnn_backward and its kin, then cgr_gnn_input_grads)
+template <class V>
+static size_t workspace_regions(const Dims& d, WorkspaceView& w, V& v) {
   const size_t N = (size_t)d.N, E = (size_t)d.E, Hp = (size_t)d.Hp;
-  W.dpre = b.take(4 * E * Hp * (size_t)d.D);  // one per layer (gnn_bwd.hip)
-  W.dm = b.take(4 * E * Hp);
-  W.dh0 = b.take(4 * E * Hp);
-  W.dzn = b.take(4 * N * Hp);
-  W.ds = b.take(4 * N * Hp);
-  W.Gs = b.take(4 * N * Hp);
+  // public names: only what gnn_backward_impl leaves complete in fp32 on every path
+  // (gnn_bwd.hip): Gs exists as an e-image alone on the split-bf16 paths, dm holds hand-off rows
+  // only
+  v.layers("dpre", w.dpre, E * Hp, d.D);  // one per layer (gnn_bwd.hip)
+  v(w.dm, E * Hp);
+  v("dpre0", w.dh0, E * Hp);  // dpre0 is written in place of dh0
+  // "dzn_main": dzn [N, Hp] where the backward materialises it in fp32 on the caller's stream for
+  // the readout NT -- below the fused level (cgr_gnn_encode_backward,
+  // cgr_gnn_encode_nodes_backward) and under max pooling.  ("dzn" stays unknown: the fused add /
+  // mean backward on the split-bf16 path never stores it.)
+  v("dzn_main", w.dzn, N * Hp);
+  v("ds", w.ds, N * Hp);
+  v(w.Gs, N * Hp);
   // e-images: only where a site lists the split-bf16 family (not in CGR_PRECISION_FP32)
   bool eimg = false;
   for (WgSite s : {WgSite::Readout, WgSite::Layer, WgSite::Node}) {
-    const WgCandidates w = wgrad_candidates(s, d);
-    for (int i = 0; i < w.n; ++i) eimg = eimg || w.c[i].family == WgFamily::B3;
+    const WgCandidates c = wgrad_candidates(s, d);
+    for (int i = 0; i < c.n; ++i) eimg = eimg || c.c[i].family == WgFamily::B3;
   }
-  W.img_side = b.take(eimg ? b3_eimg_bytes(std::max(d.E, d.N), d.H) : 0);
-  W.img_main = b.take(eimg ? b3_eimg_bytes(d.N, d.H) : 0);
-  W.img_top = b.take(eimg ? b3_eimg_bytes(d.E, d.H) : 0);
+  v(w.img_side, eimg ? b3_eimg_bytes(std::max(d.E, d.N), d.H) : 0);
+  v(w.img_main, eimg ? b3_eimg_bytes(d.N, d.H) : 0);
+  v(w.img_top, eimg ? b3_eimg_bytes(d.E, d.H) : 0);
   // split-K slabs: the largest over every family a site may pick for these dims (wgrad.hpp, the
   // table gnn_bwd.hip launches through).  The side-stream weight gradients (readout, layers, edge
-  // features) run one after another and share `slab`; the node weight gradient runs beside them
-  // on the caller's stream: `slab2`.
-  auto fit = [&](WgSite s, size_t* slab, size_t* bslab) {
-    const WgCandidates w = wgrad_candidates(s, d);
-    for (int i = 0; i < w.n; ++i) {
-      *slab = std::max(*slab, w.c[i].slab_elems());
-      *bslab = std::max(*bslab, w.c[i].bslab_elems());
+  // features) run one after another and share `slab` (two, alternating: gnn_bwd.hip); the node
+  // weight gradient runs beside them on the caller's stream: `slab2`.
+  size_t slab = 0, bslab = 0, slab2 = 0, bslab2 = 0;
+  auto fit = [&](WgSite s, size_t* sl, size_t* bs) {
+    const WgCandidates c = wgrad_candidates(s, d);
+    for (int i = 0; i < c.n; ++i) {
+      *sl = std::max(*sl, c.c[i].slab_elems());
+      *bs = std::max(*bs, c.c[i].bslab_elems());
     }
   };
-  for (WgSite s : {WgSite::Readout, WgSite::Layer, WgSite::Edge})
-    fit(s, &W.slab_elems, &W.bslab_elems);
-  fit(WgSite::Node, &W.slab2_elems, &W.bslab2_elems);
-  W.slab = b.take(4 * std::max<size_t>(W.slab_elems, 1));
-  W.bslab = b.take(4 * std::max<size_t>(W.bslab_elems, 1));
-  W.slab_b = b.take(4 * std::max<size_t>(W.slab_elems, 1));  // alternating with slab (gnn_bwd.hip)
-  W.bslab_b = b.take(4 * std::max<size_t>(W.bslab_elems, 1));
-  W.slab2 = b.take(4 * std::max<size_t>(W.slab2_elems, 1));
-  W.bslab2 = b.take(4 * std::max<size_t>(W.bslab2_elems, 1));
-  W.dag = b.take(2 * 4 * N * Hp);  // two, alternating by layer
-  // segment tickets, then one unpaired grid counter per fused layer-backward launch
-  W.cnt = b.take(4 * (N * (size_t)layer_cols(d).tiles + CGR_MAX_DEPTH));
-  W.part = b.take(4 * (size_t)bwd_seg_tiles(d) * 2 * (size_t)layer_cols(d).nf * 16);
-  W.wxT = b.take(4 * (size_t)d.F * (size_t)input_grad_ldw(d.H));
-  W.dsig_blocks = bwd_dsig_slots(d);
-  W.dsig_part = b.take(4 * (size_t)d.D * (size_t)W.dsig_blocks);
-  W.bytes = b.off;
-  return W;
+  for (WgSite s : {WgSite::Readout, WgSite::Layer, WgSite::Edge}) fit(s, &slab, &bslab);
+  fit(WgSite::Node, &slab2, &bslab2);
+  for (int k = 0; k < 2; ++k) {
+    v.floored(w.slab[k], slab);
+    v.floored(w.bslab[k], bslab);
+  }
+  v.floored(w.slab2, slab2);
+  v.floored(w.bslab2, bslab2);
+  v(w.dag, 2 * N * Hp);  // two, alternating by layer
+  v(w.cnt, N * (size_t)layer_cols(d).tiles + CGR_MAX_DEPTH);
+  v(w.part, (size_t)bwd_seg_tiles(d) * 2 * (size_t)layer_cols(d).nf * 16);
+  v(w.wxT, (size_t)d.F * (size_t)input_grad_ldw(d.H));
+  v(w.dsig_part, (size_t)d.D * (size_t)bwd_dsig_slots(d));
+  return v.off;
 }
 
+WorkspaceView workspace_view(const Dims& d, void* workspace) {
+  WorkspaceView w;
+  Placer<> v{static_cast<char*>(workspace)};
+  workspace_regions(d, w, v);
+  return w;
+}
 static int validate_config(const cgr_gnn_config* c) {
   CGR_CHECK(c != nullptr, "cgr: config is NULL");
   CGR_CHECK(c->num_node_features >= 0, "cgr: num_node_features must be >= 0");
@@ -376,62 +332,36 @@ int cgr_gnn_num_params(const cgr_gnn_config* cfg) {
 
 int64_t cgr_gnn_arena_bytes(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B) {
   if (validate_config(cfg)) return -1;
-  return (int64_t)arena_layout(make_dims(cfg, N, E, B)).bytes;
+  ArenaView a;
+  Placer<> v;
+  return (int64_t)train_regions(make_dims(cfg, N, E, B), a, v);
 }
 
 int64_t cgr_gnn_workspace_bytes(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B) {
   if (validate_config(cfg)) return -1;
-  return (int64_t)workspace_layout(make_dims(cfg, N, E, B)).bytes;
+  WorkspaceView w;
+  Placer<> v;
+  return (int64_t)workspace_regions(make_dims(cfg, N, E, B), w, v);
 }
 
+// the offset queries: the names the region statements carry; -1 for any other name, an absent
+// region or an index out of range
 int64_t cgr_gnn_arena_offset(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B,
                              const char* name, int32_t index) {
   if (validate_config(cfg) || name == nullptr) return -1;
-  const ArenaLayout L = arena_layout(make_dims(cfg, N, E, B));
-  size_t o = (size_t)-1;
-  const std::string n(name);
-  const bool li = index >= 0 && index <= CGR_MAX_DEPTH;
-  if (n == "status") o = L.status;
-  if (n == "rng") o = L.rng;
-  else if (n == "perm") o = L.perm;
-  else if (n == "src_s") o = L.src_s;
-  else if (n == "dst_s") o = L.dst_s;
-  else if (n == "rev_s") o = L.rev_s;
-  else if (n == "src_list") o = L.src_list;
-  else if (n == "dst_ptr") o = L.dst_ptr;
-  else if (n == "src_ptr") o = L.src_ptr;
-  else if (n == "graph_ptr") o = L.graph_ptr;
-  else if (n == "node_graph") o = L.node_graph;
-  else if (n == "e_s") o = L.e_s;
-  else if (n == "P") o = L.P;
-  else if (n == "Q") o = L.Q;
-  else if (n == "h" && li) o = L.h[index];
-  else if (n == "a" && li) o = L.a[index];
-  else if (n == "pre" && li) o = L.pre[index];
-  else if (n == "zn") o = L.zn;
-  else if (n == "hn") o = L.hn;
-  else if (n == "g") o = L.g;
-  return o == (size_t)-1 ? -1 : (int64_t)o;
+  ArenaView a;
+  Placer<FindName> v{nullptr, {name, index}};
+  train_regions(make_dims(cfg, N, E, B), a, v);
+  return v.note.found;
 }
 
 int64_t cgr_gnn_workspace_offset(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B,
                                  const char* name, int32_t index) {
   if (validate_config(cfg) || name == nullptr) return -1;
-  const Dims d = make_dims(cfg, N, E, B);
-  const WorkspaceLayout W = workspace_layout(d);
-  const std::string n(name);
-  // only what gnn_backward_impl leaves complete in fp32 on every path (gnn_bwd.hip): dzn and Gs
-  // exist as e-images alone on the split-bf16 paths, dm holds hand-off rows only
-  if (n == "dpre" && index >= 0 && index < d.D)
-    return (int64_t)(W.dpre + (size_t)index * 4 * (size_t)d.E * (size_t)d.Hp);
-  if (n == "dpre0") return (int64_t)W.dh0;
-  if (n == "ds") return (int64_t)W.ds;
-  // "dzn_main": dzn [N, Hp] where the backward materialises it in fp32 on the caller's stream for
-  // the readout NT -- below the fused level (cgr_gnn_encode_backward,
-  // cgr_gnn_encode_nodes_backward) and under max pooling.  ("dzn" stays unknown: the fused add /
-  // mean backward on the split-bf16 path never stores it.)
-  if (n == "dzn_main") return (int64_t)W.dzn;
-  return -1;
+  WorkspaceView w;
+  Placer<FindName> v{nullptr, {name, index}};
+  workspace_regions(make_dims(cfg, N, E, B), w, v);
+  return v.note.found;
 }
 
 int cgr_graph_prep(const cgr_gnn_config* cfg, const cgr_batch* b, void* arena, void* stream) {
@@ -442,10 +372,9 @@ int cgr_graph_prep(const cgr_gnn_config* cfg, const cgr_batch* b, void* arena, v
   if (rc) return rc;
   CGR_CHECK(arena != nullptr, "cgr: arena is NULL");
   const Dims d = make_dims(cfg, b->num_nodes, b->num_edges, b->num_graphs);
-  const ArenaLayout L = arena_layout(d);
-  const FloatView fv = float_view(arena, L, d);
+  const ArenaView av = arena_view(d, false, arena);
   PrepArgs pa{b->edge_index, b->batch, b->graph_ptr, b->edge_attr, d.N, d.E, d.B,
-              d.Fe,          d.Fep,   index_view(arena, L), fv.e_s};
+              d.Fe,          d.Fep,   av.idx,       av.flt.e_s};
   return cgr_graph_prep_impl(pa, (hipStream_t)stream);
 }
 
@@ -651,7 +580,9 @@ int cgr_gnn_encode_nodes_input_grads(const cgr_gnn_config* cfg, const float* con
 
 int64_t cgr_gnn_image_bytes(const cgr_gnn_config* cfg) {
   if (validate_config(cfg)) return -1;
-  return (int64_t)image_layout(make_dims(cfg, 1, 2, 1)).bytes;
+  Images im;
+  Placer<> v;
+  return (int64_t)image_buffer_regions(make_dims(cfg, 1, 2, 1), im, v);
 }
 
 int cgr_gnn_pack_images(const cgr_gnn_config* cfg, const float* const* params, void* images,
@@ -663,13 +594,15 @@ int cgr_gnn_pack_images(const cgr_gnn_config* cfg, const float* const* params, v
   const int np = cgr_gnn_num_params(cfg);
   for (int i = 0; i < np; ++i) CGR_CHECK(params[i] != nullptr, "cgr: NULL parameter pointer");
   const Dims d = make_dims(cfg, 1, 2, 1);
-  HIP_RET(pack_forward_images(d, params, image_layout(d), images, (hipStream_t)stream));
+  HIP_RET(pack_forward_images(d, params, image_view(d, images), (hipStream_t)stream));
   return 0;
 }
 
 int64_t cgr_gnn_predict_arena_bytes(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B) {
   if (validate_config(cfg)) return -1;
-  return (int64_t)eval_arena_layout(make_dims(cfg, N, E, B)).bytes;
+  ArenaView a;
+  Placer<> v;
+  return (int64_t)eval_regions(make_dims(cfg, N, E, B), a, v);
 }
 
 // cgr_gnn_predict (y [B]) / cgr_gnn_encode_predict (out = g_out [B, H]) /

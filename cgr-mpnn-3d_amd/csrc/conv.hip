@@ -17,46 +17,40 @@ int csr_from_keys(const int* key, int n, int nb, int* deg, int* cursor, int* ptr
 
 namespace {
 
-struct ConvLayout {
-  size_t src_c, dst_c, perm, dst_ptr, src_perm, src_ptr, deg, cursor;  // ints
-  size_t h_p, a_p, dout_p, dm, da, wT, slab, bslab, inv_deg;           // floats
-  size_t bytes;
+struct ConvScratch {
+  Reg<int> src_c, dst_c, perm, dst_ptr, src_perm, src_ptr, deg, cursor;
+  Reg<float> h_p, a_p, dout_p, dm, da, wT, slab, bslab, inv_deg;
 };
 
-ConvLayout conv_layout(int64_t N, int64_t E, int64_t H) {
-  ConvLayout L;
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    const size_t o = off;
-    off = (size_t)round_up((int64_t)(off + b), (int64_t)kAlign);
-    return o;
-  };
+// the standalone conv's scratch: every region stated once (layout.hpp); returns the total bytes
+size_t conv_regions(int64_t N, int64_t E, int64_t H, ConvScratch& s, Placer<>& v) {
   const size_t Hp = (size_t)round_up(H, 4);
-  L.src_c = take(4 * E);
-  L.dst_c = take(4 * E);
-  L.perm = take(4 * E);
-  L.dst_ptr = take(4 * (N + 1));
-  L.src_perm = take(4 * E);
-  L.src_ptr = take(4 * (N + 1));
-  L.deg = take(4 * N);
-  L.cursor = take(4 * N);
-  L.h_p = take(4 * E * Hp);
-  L.a_p = take(4 * N * Hp);
-  L.dout_p = take(4 * E * Hp);
-  L.dm = take(4 * E * Hp);
-  L.da = take(4 * N * Hp);
-  L.wT = take(4 * H * Hp);
+  v(s.src_c, E);
+  v(s.dst_c, E);
+  v(s.perm, E);
+  v(s.dst_ptr, N + 1);
+  v(s.src_perm, E);
+  v(s.src_ptr, N + 1);
+  v(s.deg, N);
+  v(s.cursor, N);
+  v(s.h_p, E * Hp);
+  v(s.a_p, N * Hp);
+  v(s.dout_p, E * Hp);
+  v(s.dm, E * Hp);
+  v(s.da, N * Hp);
+  v(s.wT, H * Hp);
   const WgChoice wg = wg_f32((int)H, (int)H, (int)E);  // dW = dout^T m (backward)
-  L.slab = take(4 * wg.slab_elems());
-  L.bslab = take(4 * wg.bslab_elems());
-  L.inv_deg = take(4 * N);
-  L.bytes = off;
-  return L;
+  v(s.slab, wg.slab_elems());
+  v(s.bslab, wg.bslab_elems());
+  v(s.inv_deg, N);
+  return v.off;
 }
 
-template <class T>
-T* P(void* base, size_t off) {
-  return reinterpret_cast<T*>(static_cast<char*>(base) + off);
+ConvScratch conv_scratch(int64_t N, int64_t E, int64_t H, void* scratch) {
+  ConvScratch s;
+  Placer<> v{static_cast<char*>(scratch)};
+  conv_regions(N, E, H, s, v);
+  return s;
 }
 
 // da[v, :] += g[v, :H]  (g unpadded [N, H])
@@ -91,7 +85,9 @@ extern "C" {
 
 int64_t cgr_dmpnn_conv_scratch_bytes(int64_t num_nodes, int64_t num_edges, int64_t hidden) {
   if (num_nodes < 1 || num_edges < 0 || hidden < 1) return -1;
-  return (int64_t)conv_layout(num_nodes, num_edges, hidden).bytes;
+  ConvScratch s;
+  Placer<> v;
+  return (int64_t)conv_regions(num_nodes, num_edges, hidden, s, v);
 }
 
 int cgr_dmpnn_conv_forward(const int64_t* edge_index, int64_t N, int64_t E, const float* h,
@@ -105,33 +101,25 @@ int cgr_dmpnn_conv_forward(const int64_t* edge_index, int64_t N, int64_t E, cons
   CGR_CHECK(N >= 1 && E >= 2 && E % 2 == 0 && H >= 1 && E < (1ll << 30) && N < (1ll << 31),
             "cgr_dmpnn_conv_forward: bad sizes (E must be even and > 0)");
   hipStream_t st = (hipStream_t)stream;
-  const ConvLayout L = conv_layout(N, E, H);
+  const ConvScratch s = conv_scratch(N, E, H, scratch);
   const int Hp = (int)round_up(H, 4);
-  int* src_c = P<int>(scratch, L.src_c);
-  int* dst_c = P<int>(scratch, L.dst_c);
-  int rc = split_edges(edge_index, (int)E, (int)N, src_c, dst_c, st);
+  int rc = split_edges(edge_index, (int)E, (int)N, s.src_c, s.dst_c, st);
   if (rc) return rc;
-  rc = csr_from_keys(dst_c, (int)E, (int)N, P<int>(scratch, L.deg), P<int>(scratch, L.cursor),
-                     P<int>(scratch, L.dst_ptr), P<int>(scratch, L.perm), st);
+  rc = csr_from_keys(s.dst_c, (int)E, (int)N, s.deg, s.cursor, s.dst_ptr, s.perm, st);
   if (rc) return rc;
-  rc = csr_from_keys(src_c, (int)E, (int)N, P<int>(scratch, L.deg), P<int>(scratch, L.cursor),
-                     P<int>(scratch, L.src_ptr), P<int>(scratch, L.src_perm), st);
+  rc = csr_from_keys(s.src_c, (int)E, (int)N, s.deg, s.cursor, s.src_ptr, s.src_perm, st);
   if (rc) return rc;
-  float* h_p = P<float>(scratch, L.h_p);
-  float* a_p = P<float>(scratch, L.a_p);
-  HIP_RET(hipMemcpy2DAsync(h_p, Hp * 4, h, H * 4, H * 4, E, hipMemcpyDeviceToDevice, st));
-  HIP_RET(segment_sum(h_p, Hp, P<int>(scratch, L.perm), P<int>(scratch, L.dst_ptr), N, Hp, a_p,
-                      Hp, st));
+  HIP_RET(hipMemcpy2DAsync(s.h_p, Hp * 4, h, H * 4, H * 4, E, hipMemcpyDeviceToDevice, st));
+  HIP_RET(segment_sum(s.h_p, Hp, s.perm, s.dst_ptr, N, Hp, s.a_p, Hp, st));
   if (aggregation == CGR_AGGR_MEAN) {  // the mean: a / max(in-degree, 1), kept for the backward
-    float* inv = P<float>(scratch, L.inv_deg);
-    HIP_RET(mean_scales(P<int>(scratch, L.dst_ptr), N, nullptr, 0, inv, nullptr, st));
-    HIP_RET(scale_rows(a_p, Hp, N, inv, st));
+    HIP_RET(mean_scales(s.dst_ptr, N, nullptr, 0, s.inv_deg, nullptr, st));
+    HIP_RET(scale_rows(s.a_p, Hp, N, s.inv_deg, st));
   }
-  HIP_RET(hipMemcpy2DAsync(a_out, H * 4, a_p, Hp * 4, H * 4, N, hipMemcpyDeviceToDevice, st));
+  HIP_RET(hipMemcpy2DAsync(a_out, H * 4, s.a_p, Hp * 4, H * 4, N, hipMemcpyDeviceToDevice, st));
   const int vw = vec_for(weight, H, H);
   hipError_t e = with_vec(vw, [&](auto VW) {
     return with_nt_rn((int)H, [&](auto RN) {
-      LdGatherDiff<true> al{a_p, h_p, src_c, nullptr, Hp};
+      LdGatherDiff<true> al{s.a_p, s.h_p, s.src_c, nullptr, Hp};
       LdPlain<decltype(VW)::value> bl{weight, H};
       EpStore ep{h_out, H, (int)E, (int)H, bias};
       return launch_gemm_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, (int)E, (int)H, (int)H, st);
@@ -154,57 +142,45 @@ int cgr_dmpnn_conv_backward(const int64_t* edge_index, int64_t N, int64_t E, con
             "cgr_dmpnn_conv_backward: unknown aggregation");
   CGR_CHECK(N >= 1 && E >= 2 && E % 2 == 0 && H >= 1, "cgr_dmpnn_conv_backward: bad sizes");
   hipStream_t st = (hipStream_t)stream;
-  const ConvLayout L = conv_layout(N, E, H);
+  const ConvScratch s = conv_scratch(N, E, H, scratch);
   const int Hp = (int)round_up(H, 4);
-  float* h_p = P<float>(scratch, L.h_p);
-  float* a_p = P<float>(scratch, L.a_p);
-  float* dout_p = P<float>(scratch, L.dout_p);
-  float* dm = P<float>(scratch, L.dm);
-  float* da = P<float>(scratch, L.da);
-  float* wT = P<float>(scratch, L.wT);
-  const int* src_c = P<int>(scratch, L.src_c);
-  const int* dst_c = P<int>(scratch, L.dst_c);
   if (grad_h_out) {
-    HIP_RET(hipMemcpy2DAsync(dout_p, Hp * 4, grad_h_out, H * 4, H * 4, E, hipMemcpyDeviceToDevice,
+    HIP_RET(hipMemcpy2DAsync(s.dout_p, Hp * 4, grad_h_out, H * 4, H * 4, E, hipMemcpyDeviceToDevice,
                              st));
     // dW = dout^T m, db = colsum(dout)
     {
-      LdPlain<4> al{dout_p, Hp};
-      LdGatherDiff<true> bl{a_p, h_p, src_c, nullptr, Hp};
-      const WgChoice wg = wg_f32((int)H, (int)H, (int)E);  // as conv_layout sized the slabs
-      float* slab = P<float>(scratch, L.slab);
-      float* bslab = P<float>(scratch, L.bslab);
-      HIP_RET(wg_f32_launch(wg, al, bl, slab, bslab, true, st));
-      HIP_RET(reduce_slabs(slab, bslab, wg.plan.splits, wg.Nout, wg.Kout, grad_weight, H, 0,
+      LdPlain<4> al{s.dout_p, Hp};
+      LdGatherDiff<true> bl{s.a_p, s.h_p, s.src_c, nullptr, Hp};
+      const WgChoice wg = wg_f32((int)H, (int)H, (int)E);  // as conv_regions sized the slabs
+      HIP_RET(wg_f32_launch(wg, al, bl, s.slab, s.bslab, true, st));
+      HIP_RET(reduce_slabs(s.slab, s.bslab, wg.plan.splits, wg.Nout, wg.Kout, grad_weight, H, 0,
                            grad_bias, st));
     }
     TransposeJobs tj{};
-    tj.job[0] = TransposeJob{weight, H, 0, wT, Hp, (int)H, (int)H};
+    tj.job[0] = TransposeJob{weight, H, 0, s.wT, Hp, (int)H, (int)H};
     tj.n = 1;
     HIP_RET(transpose_batch(tj, st));
     hipError_t e = with_nt_rn((int)H, [&](auto RN) {
-      LdPlain<4> al{dout_p, Hp};
-      LdPlain<4> bl{wT, Hp};
-      EpStore ep{dm, Hp, (int)E, (int)H, nullptr};
+      LdPlain<4> al{s.dout_p, Hp};
+      LdPlain<4> bl{s.wT, Hp};
+      EpStore ep{s.dm, Hp, (int)E, (int)H, nullptr};
       return launch_gemm_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, (int)E, (int)H, (int)H, st);
     });
     HIP_RET(e);
-    HIP_RET(segment_sum(dm, Hp, P<int>(scratch, L.src_perm), P<int>(scratch, L.src_ptr), N, Hp, da,
-                        Hp, st));
+    HIP_RET(segment_sum(s.dm, Hp, s.src_perm, s.src_ptr, N, Hp, s.da, Hp, st));
   } else {
     HIP_RET(hipMemsetAsync(grad_weight, 0, sizeof(float) * H * H, st));
     HIP_RET(hipMemsetAsync(grad_bias, 0, sizeof(float) * H, st));
-    HIP_RET(hipMemsetAsync(dm, 0, sizeof(float) * E * Hp, st));
-    HIP_RET(hipMemsetAsync(da, 0, sizeof(float) * N * Hp, st));
+    HIP_RET(hipMemsetAsync(s.dm, 0, sizeof(float) * E * Hp, st));
+    HIP_RET(hipMemsetAsync(s.da, 0, sizeof(float) * N * Hp, st));
   }
   if (grad_a) {
-    hipLaunchKernelGGL(k_add_rows, dim3(cdiv(N * H, 256)), dim3(256), 0, st, da, N, (int)H, Hp,
+    hipLaunchKernelGGL(k_add_rows, dim3(cdiv(N * H, 256)), dim3(256), 0, st, s.da, N, (int)H, Hp,
                        grad_a);
     HIP_RET(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_conv_dh, dim3(cdiv(E * H, 256)), dim3(256), 0, st, da, dm, dst_c, E, (int)H,
-                     Hp, grad_h,
-                     aggregation == CGR_AGGR_MEAN ? P<float>(scratch, L.inv_deg) : nullptr);
+  hipLaunchKernelGGL(k_conv_dh, dim3(cdiv(E * H, 256)), dim3(256), 0, st, s.da, s.dm, s.dst_c, E,
+                     (int)H, Hp, grad_h, aggregation == CGR_AGGR_MEAN ? s.inv_deg : nullptr);
   HIP_RET(hipGetLastError());
   return 0;
 }

@@ -24,8 +24,8 @@
 // stream only at the very end.
 //
 // Weight gradients: wgrad.hpp's wgrad_pick says which TN family runs a site and with which plan
-// (the table workspace_layout sized the slabs from); each site names its operands once per family
-// form and calls the `wgrad` helper below (slab check, launch, split-K reduction).
+// (the table workspace_regions, capi.hip, sized the slabs from); each site names its operands once
+// per family form and calls the `wgrad` helper below (slab check, launch, split-K reduction).
 #include "dispatch.hpp"
 #include "ep_bwd.hpp"
 #include "epilogues.hpp"
@@ -35,8 +35,6 @@
 #include "streams.hpp"
 
 namespace cgr {
-
-void dropout_params(const float* dropout_p, int training, int l, uint32_t* thresh, float* scale);
 
 // profile class of a weight gradient: the plain name for the split-bf16 e-image TN, "<name>[tnr]" /
 // "<name>[f32]" for the fp32 families, so the family is visible in the per-class report (tests
@@ -70,42 +68,22 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
                       const float* dropout_p, uint64_t seed, int training, const void* arena,
                       const float* dy, float* const* grads, void* workspace,
                       hipEvent_t const* bucket_events, hipStream_t st, OutLevel level) {
-  const ArenaLayout L = arena_layout(d);
-  const IndexView iv = index_view(const_cast<void*>(arena), L);
-  const FloatView fv = float_view(const_cast<void*>(arena), L, d);
-  const WorkspaceLayout WL = workspace_layout(d);
-  char* ws = static_cast<char*>(workspace);
-  float* dm = reinterpret_cast<float*>(ws + WL.dm);
-  float* dh0 = reinterpret_cast<float*>(ws + WL.dh0);
-  float* dzn = reinterpret_cast<float*>(ws + WL.dzn);
-  float* ds = reinterpret_cast<float*>(ws + WL.ds);
-  float* Gs = reinterpret_cast<float*>(ws + WL.Gs);
-  // side-stream slab buffers, alternating: a TN writes one while the previous weight gradient's
-  // slabs in the other are reduced in its prologue
-  float* slabs[2] = {reinterpret_cast<float*>(ws + WL.slab),
-                     reinterpret_cast<float*>(ws + WL.slab_b)};
-  float* bslabs[2] = {reinterpret_cast<float*>(ws + WL.bslab),
-                      reinterpret_cast<float*>(ws + WL.bslab_b)};
+  const ArenaView av = arena_view(d, false, const_cast<void*>(arena));
+  const IndexView& iv = av.idx;
+  const FloatView& fv = av.flt;
+  const WorkspaceView ws = workspace_view(d, workspace);
+  // ws.slab / ws.bslab, the side stream's slab buffers, alternate: a TN writes one while the
+  // previous weight gradient's slabs in the other are reduced in its prologue
   int sb = 0;  // buffer of the next side-stream TN
-  float* slab2 = reinterpret_cast<float*>(ws + WL.slab2);
-  float* bslab2 = reinterpret_cast<float*>(ws + WL.bslab2);
-  float* dsig_part = reinterpret_cast<float*>(ws + WL.dsig_part);
-  void* img_side = ws + WL.img_side;
-  void* img_main = ws + WL.img_main;
-  void* img_top = ws + WL.img_top;
   // partial sums of tile-crossing segments, accumulated by layer l's fused backward GEMM: two
   // buffers, alternating by layer (a segment's completer zeroes its entries of the next one)
-  auto dag_of = [&](int l) {
-    return reinterpret_cast<float*>(ws + WL.dag) + (l & 1) * (int64_t)d.N * d.Hp;
-  };
+  auto dag_of = [&](int l) { return ws.dag + (l & 1) * (int64_t)d.N * d.Hp; };
 
   const int N = (int)d.N, E = (int)d.E, H = d.H, Hp = d.Hp, F = d.F, Fe = d.Fe, D = d.D;
   // dpre of layer l: a buffer per layer, so that writing dpre_{l-1} never waits for the side
   // stream's weight gradient of layer l+1 (a cross-queue edge on the critical chain of a
   // captured step: ~5 us each)
-  auto dpre = [&](int l) {
-    return reinterpret_cast<float*>(ws + WL.dpre) + (int64_t)l * E * Hp;
-  };
+  auto dpre = [&](int l) { return ws.dpre + (int64_t)l * E * Hp; };
 
   SideStreams* ss = side_streams(st);
   if (!ss) return CGR_ERR_HIP;
@@ -137,7 +115,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   };
   // One weight gradient: the picked family's TN (operands as wgrad_launch takes them, wgrad.hpp)
   // into a slab pair checked to hold its plan, and its split-K reduction into o.  Side stream
-  // (readout, layer, edge) into slabs[sb]: a split-bf16 TN reduces pend's slabs in its prologue
+  // (readout, layer, edge) into ws.slab[sb]: a split-bf16 TN reduces pend's slabs in its prologue
   // and leaves its own pending, an fp32 TN is followed by one launch for both; `bucket` is
   // complete then.  Node: caller's stream, slab2, reduced at once (flat after a split-bf16 TN:
   // this one ends the backward's main chain).
@@ -148,10 +126,9 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     constexpr bool own = S == WgSite::Node;
     const bool b3 = c.family == WgFamily::B3;
     hipStream_t ws_st = own ? st : side;
-    float* sl = own ? slab2 : slabs[sb];
-    float* bsl = own ? bslab2 : bslabs[sb];
-    CGR_CHECK(c.slab_elems() <= (own ? WL.slab2_elems : WL.slab_elems) &&
-                  c.bslab_elems() <= (own ? WL.bslab2_elems : WL.bslab_elems),
+    const Reg<float>& sl = own ? ws.slab2 : ws.slab[sb];
+    const Reg<float>& bsl = own ? ws.bslab2 : ws.bslab[sb];
+    CGR_CHECK(c.slab_elems() <= sl.count && c.bslab_elems() <= bsl.count,
               "cgr: a weight-gradient plan exceeds the split-K slabs the workspace was sized for");
     {
       ProfScope _p(wgrad_class(S, c.family), ws_st);
@@ -209,7 +186,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   auto form_dzn = [&](hipStream_t s) -> int {
     ProfScope _p(readout_act_bwd_class(level), s);
     HIP_RET(readout_act_bwd(up, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act,
-                            dzn_main || !ro_b3 ? dzn : nullptr, ro_b3 ? img_side : nullptr, s,
+                            dzn_main || !ro_b3 ? ws.dzn : nullptr, ro_b3 ? ws.img_side : nullptr, s,
                             fv.inv_cnt, fv.pool_arg, fv.g));
     return 0;
   };
@@ -224,7 +201,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
       if (const int rc = form_dzn(side)) return rc;
     // dW_n = dzn^T [x | s], db_n; bucket 0 (edge_to_node, ffn) is complete once its reduction
     // has run.  With x padded to Fp the reduce skips the pad columns.
-    return wgrad(WgAt<WgSite::Readout>{}, ro, img_side, dzn, vec_for(xb, ldx, F),
+    return wgrad(WgAt<WgSite::Readout>{}, ro, ws.img_side, ws.dzn, vec_for(xb, ldx, F),
                  [&](auto V) {
                    return LdConcat<decltype(V)::value>{xb, ldx, fv.a[D], Hp, Fx};
                  },
@@ -237,15 +214,15 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   auto readout_nt = [&]() -> int {
     ProfScope _p("gemm_nt_readout_bwd", st);
     const float* m = d.act == ACT_RELU ? fv.hn : fv.zn;
-    const b3_u4* img = static_cast<const b3_u4*>(fv.b3rob);
+    const b3_u4* img = static_cast<const b3_u4*>(fv.b3rob.p);
     if (dzn_main) {  // ds = dzn W_n[:, F:] with dzn materialised (its per-element arg-max mask is
                      // no row / column factor); the image is unscaled (gnn_fwd.hip)
-      const EpStoreRowScale ep{ds, Hp, N, H, nullptr, iv.node_graph, nullptr, fv.inv_deg};
-      HIP_RET(launch_b3nt(LdPlain<4>{dzn, Hp}, img, readout_cols(d), ep, N, H, H, st, acc));
+      const EpStoreRowScale ep{ws.ds, Hp, N, H, nullptr, iv.node_graph, nullptr, fv.inv_deg};
+      HIP_RET(launch_b3nt(LdPlain<4>{ws.dzn, Hp}, img, readout_cols(d), ep, N, H, H, st, acc));
       return 0;
     }
     // (mean pooling: dy / graph count; mean aggregation: ds / in-degree, for dh_D = ds[dst])
-    const EpStoreRowScale ep{ds, Hp, N, H, dy, iv.node_graph, fv.inv_cnt, fv.inv_deg};
+    const EpStoreRowScale ep{ws.ds, Hp, N, H, dy, iv.node_graph, fv.inv_cnt, fv.inv_deg};
     const B3Cols rc = readout_cols(d);  // the image's tiling (gnn_fwd.hip)
     // the activation derivative in the A loader, specialised per activation (main-loop code)
     if (d.act == ACT_RELU)
@@ -267,22 +244,20 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   if (const int rc = readout_nt()) return rc;
 
   // learnable-skip partial-sum slots per layer (bwd_dsig_slots)
-  const int nb = WL.dsig_blocks;
+  const int nb = bwd_dsig_slots(d);
   // row tile of the fused layer-backward GEMMs: crossing segments accumulate in dag
   const int seg_rows = b3nt_rows(E, H);
   const B3Cols lcols = layer_cols(d);  // the layer images' tiling (gnn_fwd.hip)
   const int seg_cols = lcols.tiles;
   const int seg_tiles = bwd_seg_tiles(d);
-  int* cnt = reinterpret_cast<int*>(ws + WL.cnt);
   const int spin = unpaired_spin_limit();  // CGR_UNPAIRED_SPIN_LIMIT (debug knob), per call
-  float* part = reinterpret_cast<float*>(ws + WL.part);
   auto layer_args = [&](int l) {
     uint32_t thresh;
     float scale;
-    dropout_params(dropout_p, training, l, &thresh, &scale);
+    dropout_consts(dropout_p, training, l, &thresh, &scale);
     LayerBwdArgs la{};
-    la.ds = ds;
-    la.dm = dm;
+    la.ds = ws.ds;
+    la.dm = ws.dm;
     la.dst_s = iv.dst_s;
     la.rev_s = iv.rev_s;
     la.hnext = fv.h[l + 1];
@@ -298,7 +273,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     la.H = H;
     la.Hp = Hp;
     la.dpre = dpre(l);
-    la.dsig_part = d.learnable_skip ? dsig_part + (int64_t)l * nb : nullptr;
+    la.dsig_part = d.learnable_skip ? ws.dsig_part + (int64_t)l * nb : nullptr;
     return la;
   };
   // the top layer's weight gradient on the split-bf16 e-image TN takes dpre_{D-1}'s e-image from
@@ -313,15 +288,15 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     ProfScope _p("layer_act_bwd", st);
     LayerBwdArgs la = layer_args(D - 1);
     la.dag = dag_of(D - 1);
-    la.cnt = cnt;
+    la.cnt = ws.cnt;
     la.cnt_nodes = N;
     la.cnt_tiles = seg_cols;
     la.tile_rows = seg_rows;
-    HIP_RET(layer_act_bwd(la, nb, top_b3 ? img_top : nullptr, st));
+    HIP_RET(layer_act_bwd(la, nb, top_b3 ? ws.img_top : nullptr, st));
   }
   auto edge_args = [&]() {
     LayerBwdArgs le{};
-    le.dm = dm;
+    le.dm = ws.dm;
     le.rev_s = iv.rev_s;
     le.h0 = fv.h[0];
     le.pre = fv.pre[0];
@@ -329,8 +304,8 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     le.E = E;
     le.H = H;
     le.Hp = Hp;
-    le.dh0 = dh0;
-    le.dpre = dh0;  // dpre0 is written in place of dh0 (the buffer it names)
+    le.dh0 = ws.dh0;
+    le.dpre = ws.dh0;  // dpre0 is written in place of dh0 (the buffer it names)
     le.dpre_all = dpre(0);
     le.dpre_stride = (int64_t)E * Hp;
     le.nlayers = D;
@@ -339,7 +314,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
   };
   // edge init: dpre0 = (dh0 + dh_0) * act'(pre0), dh0 summed from the layers' dpre buffers,
   // written to the dh0 buffer
-  float* dpre0 = dh0;
+  float* dpre0 = ws.dh0;
   for (int l = D - 1; l >= 0; --l) {
     float* dp = dpre(l);  // written by the previous iteration's fused kernel (or just above)
     // main: dm = dpre W_l.  The fork point is recorded before the NT is enqueued and the side
@@ -353,30 +328,32 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     {
       ProfScope _p("gemm_nt_layer_bwd_seg", st);
       const LdGatherRows al{dp, iv.rev_s, Hp};
-      const b3_u4* img = static_cast<const b3_u4*>(fv.b3lb[l]);
+      const b3_u4* img = static_cast<const b3_u4*>(fv.b3lb[l].p);
       float* dg = dag_of(l);
       float* dgn = l > 0 ? dag_of(l - 1) : nullptr;
-      int* gcnt = cnt + (int64_t)N * seg_cols + l;  // this launch's unpaired grid counter
+      int* gcnt = ws.cnt + (int64_t)N * seg_cols + l;  // this launch's unpaired grid counter
       if (l > 0)
         HIP_RET(launch_b3nt(al, img, lcols,
-                            EpLayerBwdSeg<false>{lb, dm, iv.dst_s, iv.dst_ptr, iv.src_list,
-                                                 iv.src_ptr, dg, dgn, part, cnt, iv.status, E, H, N,
-                                                 seg_cols, gcnt, ss->dev_err, spin, fv.inv_deg},
+                            EpLayerBwdSeg<false>{lb, ws.dm, iv.dst_s, iv.dst_ptr, iv.src_list,
+                                                 iv.src_ptr, dg, dgn, ws.part, ws.cnt, iv.status,
+                                                 E, H, N, seg_cols, gcnt, ss->dev_err, spin,
+                                                 fv.inv_deg},
                             E, H, H, st, acc));
       else
         HIP_RET(launch_b3nt(al, img, lcols,
-                            EpLayerBwdSeg<true>{lb, dm, iv.dst_s, iv.dst_ptr, iv.src_list,
-                                                iv.src_ptr, dg, dgn, part, cnt, iv.status, E, H, N,
-                                                seg_cols, gcnt, ss->dev_err, spin, fv.inv_deg},
+                            EpLayerBwdSeg<true>{lb, ws.dm, iv.dst_s, iv.dst_ptr, iv.src_list,
+                                                iv.src_ptr, dg, dgn, ws.part, ws.cnt, iv.status,
+                                                E, H, N, seg_cols, gcnt, ss->dev_err, spin,
+                                                fv.inv_deg},
                             E, H, H, st, acc));
     }
     if (fork_ev) HIP_RET(hipStreamWaitEvent(side, fork_ev, 0));
     {  // side: dW_l = dpre^T m_l, db_l = colsum(dpre); the previous weight gradient's slabs are
        // reduced in the TN's prologue, this one's by the next TN (bucket D - l complete then)
-      const void* img = l == D - 1 ? img_top : img_side;  // top layer: layer_act_bwd wrote it
+      const void* img = l == D - 1 ? ws.img_top : ws.img_side;  // top layer: layer_act_bwd wrote it
       if (ly.family == WgFamily::B3 && l < D - 1) {
         ProfScope _p("eimage", side);
-        HIP_RET(b3_eimage(dp, Hp, E, H, static_cast<b3_u4*>(img_side), side));
+        HIP_RET(b3_eimage(dp, Hp, E, H, static_cast<b3_u4*>(ws.img_side.p), side));
       }
       const int rc = wgrad(WgAt<WgSite::Layer>{}, ly, img, dp, 4,
                            [&](auto) {
@@ -415,13 +392,13 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     if (nd.family == WgFamily::B3) {  // Gs straight into the TN's e-image (never stored in fp32)
       ProfScope _p("segsum_src_bwd", st);
       HIP_RET(b3_segsum_eimage(dpre0, Hp, iv.src_list, iv.src_ptr, N, H,
-                               static_cast<b3_u4*>(img_main), st));
+                               static_cast<b3_u4*>(ws.img_main.p), st));
     } else {
       ProfScope _p("segsum_src_bwd", st);
-      HIP_RET(segment_sum(dpre0, Hp, iv.src_list, iv.src_ptr, N, Hp, Gs, Hp, st));
+      HIP_RET(segment_sum(dpre0, Hp, iv.src_list, iv.src_ptr, N, Hp, ws.Gs, Hp, st));
     }
     // db0 comes from the edge-feature TN when there is one
-    const int rc = wgrad(WgAt<WgSite::Node>{}, nd, img_main, Gs, vec_for(xb, ldx, F),
+    const int rc = wgrad(WgAt<WgSite::Node>{}, nd, ws.img_main, ws.Gs, vec_for(xb, ldx, F),
                          [&](auto V) { return LdPlain<decltype(V)::value>{xb, ldx}; },
                          WgDst{gW0, F + Fe, 0, Fe > 0 ? nullptr : gb0, F, nd.Kout - F}, -1);
     if (rc) return rc;
@@ -442,7 +419,7 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
     }
     sj.n = D;
     ProfScope _p("skip_grad_reduce", st);
-    HIP_RET(reduce_partials(dsig_part, nb, sj, st));
+    HIP_RET(reduce_partials(ws.dsig_part, nb, sj, st));
   }
   if (const int rc = flush()) return rc;  // (nothing left unless an edge TN was not run)
   // join: every gradient is complete when the main stream reaches here
@@ -462,12 +439,11 @@ int gnn_backward_impl(const Dims& d, const float* const* params, const cgr_batch
 int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* arena,
                          const float* dy, void* workspace, float* dx, float* de, hipStream_t st,
                          OutLevel level) {
-  const ArenaLayout L = arena_layout(d);
-  const IndexView iv = index_view(const_cast<void*>(arena), L);
-  const FloatView fv = float_view(const_cast<void*>(arena), L, d);
-  const WorkspaceLayout WL = workspace_layout(d);
-  char* ws = static_cast<char*>(workspace);
-  const float* dpre0 = reinterpret_cast<const float*>(ws + WL.dh0);
+  const ArenaView av = arena_view(d, false, const_cast<void*>(arena));
+  const IndexView& iv = av.idx;
+  const FloatView& fv = av.flt;
+  const WorkspaceView ws = workspace_view(d, workspace);
+  const float* dpre0 = ws.dh0;
   const int N = (int)d.N, E = (int)d.E, H = d.H, Hp = d.Hp, F = d.F, Fe = d.Fe, D = d.D;
   if (de && Fe > 0) {  // de = dpre0 W0e: B = W0[:, F:]^T, the forward's w0eT [Fe, Hp]
     ProfScope _p("input_grad_edge", st);
@@ -479,29 +455,26 @@ int gnn_input_grads_impl(const Dims& d, const float* const* params, const void* 
     }));
   }
   if (dx && F > 0) {
-    float* Gs = reinterpret_cast<float*>(ws + WL.Gs);
-    float* dzn = reinterpret_cast<float*>(ws + WL.dzn);
-    float* wxT = reinterpret_cast<float*>(ws + WL.wxT);
     const int ldw = input_grad_ldw(H);
     {
       ProfScope _p("input_grad_prep", st);
-      HIP_RET(segment_sum(dpre0, Hp, iv.src_list, iv.src_ptr, N, H, Gs, Hp, st));
+      HIP_RET(segment_sum(dpre0, Hp, iv.src_list, iv.src_ptr, N, H, ws.Gs, Hp, st));
       // `dy` is the level's upstream: dy [B], dg [B, H] or dn [N, H]; wf is read at Fused only
       const ReadoutUp up{level, dy, params[CGR_PARAM_FFN_W(D)]};
-      HIP_RET(readout_act_bwd(up, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act, dzn, nullptr, st,
+      HIP_RET(readout_act_bwd(up, iv.node_graph, fv.hn, fv.zn, N, H, Hp, d.act, ws.dzn, nullptr, st,
                               fv.inv_cnt, fv.pool_arg, fv.g));
       TransposeJobs tj{};  // wxT [F, ldw] = [W0[:, :F]^T | W_n[:, :F]^T]
-      tj.job[0] = TransposeJob{params[CGR_PARAM_EDGE_INIT_W], F + Fe, 0, wxT, ldw, H, F};
-      tj.job[1] = TransposeJob{params[CGR_PARAM_E2N_W(D)], F + H, 0, wxT + H, ldw, H, F};
+      tj.job[0] = TransposeJob{params[CGR_PARAM_EDGE_INIT_W], F + Fe, 0, ws.wxT, ldw, H, F};
+      tj.job[1] = TransposeJob{params[CGR_PARAM_E2N_W(D)], F + H, 0, ws.wxT + H, ldw, H, F};
       tj.n = 2;
       HIP_RET(transpose_batch(tj, st));
     }
     ProfScope _p("input_grad_node", st);
-    const LdPlain<4> bl{wxT, ldw};
+    const LdPlain<4> bl{ws.wxT, ldw};
     const EpStore ep{dx, F, N, F, nullptr};
     // [Gs | dzn] rows: the concat boundary H must not split a VEC-wide chunk
     HIP_RET(with_vec(H % 4 == 0 ? 4 : (H % 2 == 0 ? 2 : 1), [&](auto V) {
-      const LdConcat<decltype(V)::value> al{Gs, Hp, dzn, Hp, H};
+      const LdConcat<decltype(V)::value> al{ws.Gs, Hp, ws.dzn, Hp, H};
       return with_nt_rn(F, [&](auto RN) {
         return launch_gemm_nt<4, 1, decltype(RN)::value, 1>(al, bl, ep, N, F, 2 * H, st);
       });

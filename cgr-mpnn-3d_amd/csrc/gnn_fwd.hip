@@ -23,8 +23,7 @@
 
 namespace cgr {
 
-static void dropout_consts(const float* dropout_p, int training, int l, uint32_t* thresh,
-                           float* scale) {
+void dropout_consts(const float* dropout_p, int training, int l, uint32_t* thresh, float* scale) {
   *thresh = 0;
   *scale = 1.f;
   if (!(training & CGR_TRAIN_DROPOUT) || dropout_p == nullptr) return;
@@ -42,21 +41,17 @@ static void dropout_consts(const float* dropout_p, int training, int l, uint32_t
   *scale = (float)(1.0 / (1.0 - p));
 }
 
-void dropout_params(const float* dropout_p, int training, int l, uint32_t* thresh, float* scale) {
-  dropout_consts(dropout_p, training, l, thresh, scale);
-}
-
-// every forward weight image (x-GEMM, readout, layers) into `images` (ImageLayout), one launch
-hipError_t pack_forward_images(const Dims& d, const float* const* params, const ImageLayout& IL,
-                               void* images, hipStream_t st) {
+// every forward weight image (x-GEMM, readout, layers) into a caller's image buffer (image_view),
+// one launch
+hipError_t pack_forward_images(const Dims& d, const float* const* params, const Images& im,
+                               hipStream_t st) {
   const int H = d.H, F = d.F, Fe = d.Fe, D = d.D;
   const float* W0 = params[CGR_PARAM_EDGE_INIT_W];
   const float* Wn = params[CGR_PARAM_E2N_W(D)];
-  char* base = static_cast<char*>(images);
   B3PackJobs pj{};
   hipError_t e;
   if (F > 0) {
-    b3_u4* ximg = reinterpret_cast<b3_u4*>(base + IL.b3x);
+    b3_u4* ximg = static_cast<b3_u4*>(im.b3x.p);
     const B3Cols cx = image_cols(d, 2 * H);
     if ((e = b3_pack_add(pj, B3PackJob{W0, F + Fe, 1, ximg, 0, H, H, F, cx.nimg, b3_nk(F)}, st)))
       return e;
@@ -65,10 +60,9 @@ hipError_t pack_forward_images(const Dims& d, const float* const* params, const 
       return e;
   }
   const B3Cols ch = image_cols(d, H);
-  if ((e = b3_pack_add(pj, b3_job(Wn + F, F + H, 1, H, H, base + IL.b3rof, ch), st))) return e;
+  if ((e = b3_pack_add(pj, b3_job(Wn + F, F + H, 1, H, H, im.b3rof, ch), st))) return e;
   for (int l = 0; l < D; ++l)
-    if ((e = b3_pack_add(pj, b3_job(params[CGR_PARAM_CONV_W(l)], H, 1, H, H, base + IL.b3lf[l],
-                                    ch), st)))
+    if ((e = b3_pack_add(pj, b3_job(params[CGR_PARAM_CONV_W(l)], H, 1, H, H, im.b3lf[l], ch), st)))
       return e;
   return b3_pack(pj, st);
 }
@@ -76,18 +70,17 @@ hipError_t pack_forward_images(const Dims& d, const float* const* params, const 
 int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch* b,
                      const float* dropout_p, uint64_t seed, uint64_t* rng_counter, int training,
                      void* arena, float* y, hipStream_t st, const FwdMode& mode) {
-  const ArenaLayout L = mode.eval ? eval_arena_layout(d) : arena_layout(d);
-  const IndexView iv = index_view(arena, L);
-  FloatView fv = float_view(arena, L, d);
+  ArenaView av = arena_view(d, mode.eval, arena);
+  const IndexView& iv = av.idx;
+  FloatView& fv = av.flt;
   // forward weight images pre-packed by the caller (cgr_gnn_pack_images), or packed below into
   // the arena by this call
   const bool caller_images = mode.eval && mode.images != nullptr;
   if (caller_images) {
-    const ImageLayout IL = image_layout(d);
-    char* im = static_cast<char*>(const_cast<void*>(mode.images));
-    fv.b3x = d.F > 0 ? im + IL.b3x : nullptr;
-    fv.b3rof = im + IL.b3rof;
-    for (int l = 0; l < d.D; ++l) fv.b3lf[l] = im + IL.b3lf[l];
+    const Images im = image_view(d, const_cast<void*>(mode.images));
+    fv.b3x = im.b3x;
+    fv.b3rof = im.b3rof;
+    for (int l = 0; l < d.D; ++l) fv.b3lf[l] = im.b3lf[l];
   }
   const int N = (int)d.N, E = (int)d.E, H = d.H, Hp = d.Hp, F = d.F, Fe = d.Fe, D = d.D;
   const float* W0 = params[CGR_PARAM_EDGE_INIT_W];
@@ -169,9 +162,9 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
     ProfScope _p("weight_pack", st);
     B3PackJobs pj{}, pm{};
     if (F > 0) {
-      HIP_RET(b3_pack_add(pj, B3PackJob{W0, F + Fe, 1, static_cast<b3_u4*>(fv.b3x), 0, H, H, F,
+      HIP_RET(b3_pack_add(pj, B3PackJob{W0, F + Fe, 1, static_cast<b3_u4*>(fv.b3x.p), 0, H, H, F,
                                         xcols.nimg, b3_nk(F)}, side));
-      HIP_RET(b3_pack_add(pj, B3PackJob{Wn, F + H, 1, static_cast<b3_u4*>(fv.b3x), H,
+      HIP_RET(b3_pack_add(pj, B3PackJob{Wn, F + H, 1, static_cast<b3_u4*>(fv.b3x.p), H,
                                         xcols.nimg - H, H, F, xcols.nimg, b3_nk(F)}, side));
     }
     HIP_RET(b3_pack_add(pm, b3_job(Wn + F, F + H, 1, H, H, fv.b3rof, rcols), st));
@@ -190,7 +183,7 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
                             st));
     }
     rm.z_dst = iv.zero_block;
-    rm.z_u4 = (int64_t)(iv.zero_bytes / 16);
+    rm.z_u4 = (int64_t)(iv.zero_block.count / 16);
     if (side == st) {
       for (int j = 0; j < pj.n; ++j) HIP_RET(b3_pack_add(pm, pj.job[j], st));
       rm.p_src = rx.p_src;
@@ -242,7 +235,7 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
     }
     hipError_t e = with_vec(vec_for(xa, ldx, F), [&](auto VX) {
       LdPlain<decltype(VX)::value> al{xa, ldx};
-      return launch_b3nt(al, static_cast<const b3_u4*>(fv.b3x), xcols, ep, N, 2 * H, Kx, side,
+      return launch_b3nt(al, static_cast<const b3_u4*>(fv.b3x.p), xcols, ep, N, 2 * H, Kx, side,
                          acc);
     });
     HIP_RET(e);
@@ -319,14 +312,14 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
                scale,    iv.rng,
                l};
     LdGatherDiff<false> al{fv.a[l], fv.h[l], iv.src_s, iv.rev_s, Hp};
-    const b3_u4* img = static_cast<const b3_u4*>(fv.b3lf[l]);
+    const b3_u4* img = static_cast<const b3_u4*>(fv.b3lf[l].p);
     if (fused_seg) {  // h_{l+1} and a_{l+1} = segsum_dst(h_{l+1}) from one launch
       ProfScope _p("gemm_nt_layer_seg_fwd", st);
       // eval ring: a_{l+2} reuses a_{l-1}'s buffer, free once layer l-1 read it; this layer
       // zeroes the entries layer l+1 will accumulate there
       float* znext = (mode.eval && l >= 1 && l + 2 <= D) ? fv.a[l + 2] : nullptr;
       HIP_RET(launch_b3nt(al, img, lcols,
-                          EpLayerSeg{ep, iv.dst_s, fv.a[l + 1], Hp, znext, iv.dst_ptr, iv.fpart,
+                          EpLayerSeg{ep, iv.dst_s, fv.a[l + 1], Hp, znext, iv.dst_ptr, fv.fpart,
                                      iv.fcnt, lcols.tiles},
                           E, H, H, st, acc));
     } else {
@@ -344,7 +337,7 @@ int gnn_forward_impl(const Dims& d, const float* const* params, const cgr_batch*
   {
     ProfScope _p("gemm_nt_readout_fwd", st);
     EpReadoutQ ep{bn, fv.Q, fv.hn, fv.zn, Hp, N, H, d.act};
-    HIP_RET(launch_b3nt(LdPlain<4>{fv.a[D], Hp}, static_cast<const b3_u4*>(fv.b3rof), rcols, ep,
+    HIP_RET(launch_b3nt(LdPlain<4>{fv.a[D], Hp}, static_cast<const b3_u4*>(fv.b3rof.p), rcols, ep,
                         N, H, H, st, acc));
   }
   if (mode.level == OutLevel::Nodes) {  // y names n_out [N, H]; no pool, its state untouched

@@ -1,4 +1,4 @@
-// Internal (non-ABI) declarations: arena layout, index views, launch helpers.
+// Internal (non-ABI) declarations: the views of the caller's buffers, dims, launch helpers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/cgr_mpnn3d.h"
+#include "layout.hpp"
 
 namespace cgr {
 
@@ -31,64 +32,56 @@ void set_error(const std::string& msg);
     }                                  \
   } while (0)
 
-constexpr size_t kAlign = 256;
-
 // Every launching entry point starts with this: hipGetLastError() is per thread and sticky, so an
 // error left by an unrelated earlier HIP call (e.g. a caller's aborted stream capture) would
 // otherwise be reported by our first post-launch check as if our launch had failed.
 inline void clear_stale_hip_error() { (void)hipGetLastError(); }
 
+// Views of the caller's buffers: every member is a region (layout.hpp), stated once in its
+// layout function (capi.hip) and read here as the typed pointer it converts to.
 // Index bookkeeping inside the arena (all int32).
 struct IndexView {
   // zero block (zeroed each forward: a rider of the pack launch, or a memset with caller images):
   // deg_dst, deg_src, cursor, cursor2, graph_cnt, status, fcnt
-  int* deg_dst;
-  int* deg_src;
-  int* cursor;
-  int* cursor2;
-  int* graph_cnt;
-  int* status;
-  int* fcnt;     // [N * column tiles] hub-segment tickets of the layer GEMMs (in the zero block)
-  float* fpart;  // [tiles, 2, BN] hub-segment partial sums of the layer GEMMs
-  uint64_t* rng;  // effective dropout key of this forward (read by every dropout kernel)
-  void* zero_block;
-  size_t zero_bytes;
-  int* perm;
-  int* src_s;
-  int* dst_s;
-  int* rev_s;
-  int* src_list;
-  int* inv;
-  int* src_c;
-  int* dst_c;
-  int* dst_ptr;
-  int* src_ptr;
-  int* graph_ptr;
-  int* node_graph;
+  Reg<int> deg_dst, deg_src, cursor, cursor2, graph_cnt, status;
+  Reg<int> fcnt;  // [N * column tiles] hub-segment tickets of the layer GEMMs (in the zero block)
+  Reg<void> zero_block;
+  Reg<uint64_t> rng;  // effective dropout key of this forward (read by every dropout kernel)
+  Reg<int> perm, src_s, dst_s, rev_s, src_list, inv, src_c, dst_c, dst_ptr, src_ptr, graph_ptr,
+      node_graph;
+};
+
+// split-bf16 weight images (gemm_b3.hpp), packed once per step by the forward or, the forward
+// ones, by cgr_gnn_pack_images into a buffer of the caller's
+struct Images {
+  Reg<void> b3x;                  // [W0[:, :F]; W_n[:, :F]]   (x-GEMM; F > 0)
+  Reg<void> b3rof;                // W_n[:, F:]                 (readout forward)
+  Reg<void> b3rob;                // W_n[:, F:]^T diag(wf)      (readout backward)
+  Reg<void> b3lf[CGR_MAX_DEPTH];  // W_l                        (layer forward)
+  Reg<void> b3lb[CGR_MAX_DEPTH];  // W_l^T                      (layer backward)
 };
 
 // Forward-saved float state inside the arena.
-struct FloatView {
-  float* e_s;   // [E, Fep] sorted, zero padded edge_attr
-  float* w0eT;  // [Fe, Hp] transposed edge-feature slice of edge_init.weight
-  float* P;     // [N, Hp]  x @ W0[:, :F]^T (node-level half of edge init)
-  float* Q;     // [N, Hp]  x @ W_n[:, :F]^T (x-part of the readout, computed beside graph prep)
-  float* xp;    // [N, Fp]  x with rows padded to 4 floats (only when F % 4 != 0; else nullptr)
-  float* h[CGR_MAX_DEPTH + 1];    // [E, Hp] h_0 .. h_D
-  float* a[CGR_MAX_DEPTH + 1];    // [N, Hp] a_l = scatter_add(h_l, dst); a_D = readout s
-  float* pre[CGR_MAX_DEPTH + 1];  // [E, Hp] pre-activations (non-ReLU only; else nullptr)
-  float* zn;                      // [N, Hp] readout pre-activation (non-ReLU only)
-  float* hn;                      // [N, Hp] readout activation
-  float* g;                       // [B, Hp] pooled graph embeddings
-  float* inv_deg;  // [N] 1 / max(in-degree, 1)   (mean aggregation; else nullptr)
-  float* inv_cnt;  // [B] 1 / max(graph nodes, 1) (mean pooling; else nullptr)
-  int* pool_arg;   // [B, Hp] max pooling's first arg-max node per column (else nullptr)
-  // split-bf16 weight images (gemm_b3.hpp), packed once per step by the forward:
-  void* b3x;                      // [W0[:, :F]; W_n[:, :F]]   (x-GEMM)
-  void* b3rof;                    // W_n[:, F:]                 (readout forward)
-  void* b3rob;                    // W_n[:, F:]^T diag(wf)      (readout backward)
-  void* b3lf[CGR_MAX_DEPTH];      // W_l                        (layer forward)
-  void* b3lb[CGR_MAX_DEPTH];      // W_l^T                      (layer backward)
+struct FloatView : Images {
+  Reg<float> fpart;  // [tiles, 2, BN] hub-segment partial sums of the layer GEMMs
+  Reg<float> e_s;    // [E, Fep] sorted, zero padded edge_attr (Fe > 0)
+  Reg<float> w0eT;   // [Fe, Hp] transposed edge-feature slice of edge_init.weight (Fe > 0)
+  Reg<float> P;      // [N, Hp]  x @ W0[:, :F]^T (node-level half of edge init)
+  Reg<float> Q;      // [N, Hp]  x @ W_n[:, :F]^T (x-part of the readout, beside graph prep)
+  Reg<float> xp;     // [N, Fp]  x with rows padded to 4 floats (only when F % 4 != 0)
+  Reg<float> h[CGR_MAX_DEPTH + 1];    // [E, Hp] h_0 .. h_D
+  Reg<float> a[CGR_MAX_DEPTH + 1];    // [N, Hp] a_l = scatter_add(h_l, dst); a_D = readout s
+  Reg<float> pre[CGR_MAX_DEPTH + 1];  // [E, Hp] pre-activations (non-ReLU only)
+  Reg<float> zn;                      // [N, Hp] readout pre-activation (non-ReLU only)
+  Reg<float> hn;                      // [N, Hp] readout activation
+  Reg<float> g;                       // [B, Hp] pooled graph embeddings
+  Reg<float> inv_deg;  // [N] 1 / max(in-degree, 1)   (mean aggregation only)
+  Reg<float> inv_cnt;  // [B] 1 / max(graph nodes, 1) (mean pooling only)
+  Reg<int> pool_arg;   // [B, Hp] max pooling's first arg-max node per column, -1: empty graph
+};
+struct ArenaView {
+  IndexView idx;
+  FloatView flt;
 };
 
 struct Dims {
@@ -104,46 +97,32 @@ struct Dims {
   bool nt_acc() const { return precision == CGR_PRECISION_FP32; }  // per-k-step accumulation
 };
 
-struct ArenaLayout {
-  size_t off_index_begin;
-  size_t bytes;
-  // offsets (bytes) for every buffer
-  size_t zero_block, zero_bytes, deg_dst, deg_src, cursor, cursor2, graph_cnt, status, rng;
-  size_t fcnt, fpart;
-  size_t perm, src_s, dst_s, rev_s, src_list, inv, src_c, dst_c, dst_ptr, src_ptr, graph_ptr,
-      node_graph;
-  size_t e_s, w0eT, P, Q, xp, h[CGR_MAX_DEPTH + 1], a[CGR_MAX_DEPTH + 1],
-      pre[CGR_MAX_DEPTH + 1], zn, hn, g;
-  size_t inv_deg, inv_cnt;  // mean aggregation / pooling: 1 / max(count, 1) per node / graph
-  size_t pool_arg;          // max pooling: [B, Hp] node of each pooled value (-1: empty graph)
-  size_t b3x, b3rof, b3rob, b3lf[CGR_MAX_DEPTH], b3lb[CGR_MAX_DEPTH];
-};
-
 // Backward workspace.  dpre has one buffer per layer (no side->main wait before a buffer is
 // rewritten; the edge-init backward sums dh0 from all of them); dm holds only the rows the fused
 // layer-backward GEMM hands to the completer of a tile-crossing segment (ep_bwd.hpp).
-struct WorkspaceLayout {
-  size_t bytes;
-  size_t dpre, dm, dh0, dzn, ds, Gs, slab, bslab, slab2, bslab2, dsig_part;
-  size_t slab_b, bslab_b;  // the side stream's second slab pair (reductions folded into TNs)
-  // floats each slab / bias slab holds (slab, slab_b; slab2): the backward checks the plan it
-  // picked against them before every weight-gradient launch
-  size_t slab_elems = 0, bslab_elems = 0, slab2_elems = 0, bslab2_elems = 0;
+struct WorkspaceView {
+  Reg<float> dpre;  // D x [E, Hp], layer l at l * E * Hp
+  Reg<float> dm, dh0, dzn, ds, Gs;
   // split-bf16 e-images (gemm_b3tn.hpp B3EImg) of the weight gradients' shared operand: dpre_l and
   // dzn on the side stream (one at a time), Gs on the caller's stream; the top layer's dpre,
   // written by its activation kernel on the caller's stream (img_top)
-  size_t img_side, img_main, img_top;
+  Reg<void> img_side, img_main, img_top;
+  // split-K slabs and bias slabs; count is the floats each holds: the backward checks the plan it
+  // picked against it before every weight-gradient launch.  slab[2]: the side stream's
+  // alternating pair (reductions folded into TNs); slab2: the node site's, on the caller's stream
+  Reg<float> slab[2], bslab[2], slab2, bslab2;
   // 2 x [N, Hp] partial da sums of the dst segments that cross a row tile of the fused
   // layer-backward GEMM (ep_bwd.hpp), alternating by layer
-  size_t dag;
-  // [N * column tiles + 1] ticket counters of those segments (and of the grid, unpaired form)
-  size_t cnt;
+  Reg<float> dag;
+  // [N * column tiles] ticket counters of those segments, then one unpaired grid counter per
+  // fused layer-backward launch
+  Reg<int> cnt;
   // [row tiles * column tiles, 2, BN] partial sums of the segments over >= 3 row tiles
-  size_t part;
+  Reg<float> part;
   // [F, input_grad_ldw(H)] the stacked, transposed x slices of edge_init / edge_to_node weights
   // (cgr_gnn_input_grads only)
-  size_t wxT;
-  int dsig_blocks;
+  Reg<float> wxT;
+  Reg<float> dsig_part;  // [D, bwd_dsig_slots] learnable-skip partial sums
 };
 inline int input_grad_ldw(int H) { return (2 * H + 3) & ~3; }
 int bwd_dsig_slots(const Dims& d);
@@ -179,17 +158,16 @@ struct FwdMode {
   const void* images = nullptr;
   OutLevel level = OutLevel::Fused;
 };
-struct ImageLayout {
-  size_t b3x, b3rof, b3lf[CGR_MAX_DEPTH], bytes;
-};
-ImageLayout image_layout(const Dims& d);
-
 Dims make_dims(const cgr_gnn_config* cfg, int64_t N, int64_t E, int64_t B);
-ArenaLayout arena_layout(const Dims& d);
-ArenaLayout eval_arena_layout(const Dims& d);
-WorkspaceLayout workspace_layout(const Dims& d);
-IndexView index_view(void* arena, const ArenaLayout& L);
-FloatView float_view(void* arena, const ArenaLayout& L, const Dims& d);
+// The views over a buffer, one call each (capi.hip).  arena_view: the training arena's, or the
+// eval (predict) arena's; image_view: a caller-packed image buffer's (only the forward images are
+// present).
+ArenaView arena_view(const Dims& d, bool eval, void* arena);
+WorkspaceView workspace_view(const Dims& d, void* workspace);
+Images image_view(const Dims& d, void* images);
+
+// dropout threshold and scale of layer l (gnn_fwd.hip; oracle/dropout.py models it)
+void dropout_consts(const float* dropout_p, int training, int l, uint32_t* thresh, float* scale);
 
 struct PrepArgs {
   const int64_t* edge_index;

@@ -186,9 +186,9 @@ using namespace cgr;
 
 int cgr_graph_prep_impl(const PrepArgs& a, hipStream_t st) {
   const int E = (int)a.E, N = (int)a.N, B = (int)a.B;
-  IndexView iv = a.idx;
+  const IndexView& iv = a.idx;
   // zero counters + status (one contiguous block, see arena layout)
-  if (!a.zeroed) HIP_RET(hipMemsetAsync(iv.zero_block, 0, iv.zero_bytes, st));
+  if (!a.zeroed) HIP_RET(hipMemsetAsync(iv.zero_block, 0, iv.zero_block.count, st));
   const int T = 256;
   const int nt = E + N + (a.graph_ptr ? B + 1 : 0);
   hipLaunchKernelGGL(k_prep_count, dim3(cdiv(nt > 0 ? nt : 1, T)), dim3(T), 0, st, a.edge_index,

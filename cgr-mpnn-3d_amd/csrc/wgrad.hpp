@@ -91,7 +91,7 @@ struct WgCandidates {
 };
 
 // The families a site may run for these dims, most preferred first, feasible or not: the first
-// feasible one runs (wgrad_pick), the slabs hold the largest of all of them (workspace_layout).
+// feasible one runs (wgrad_pick), the slabs hold the largest of all of them (workspace_regions).
 // x_side families read x (or xp) in 16-byte units: Fx % 4 == 0 always, the pointer is the caller's.
 inline WgCandidates wgrad_candidates(WgSite s, const Dims& d) {
   const int H = d.H, N = (int)d.N, E = (int)d.E;

@@ -174,6 +174,14 @@ SIGNATURES = [
      [c_void_p, c_void_p, c_int64, c_int32, c_double, c_void_p, c_void_p]),
     ("cgr_huber_loss_backward", c_int32,
      [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
+    # attention pooling (added within ABI 9): x, ldx, N, H, batch, ptr, B, weight, ...
+    ("cgr_attention_pool_workspace_bytes", c_int64, [c_int64, c_int64]),
+    ("cgr_attention_pool_forward", c_int32,
+     [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("cgr_attention_pool_backward", c_int32,
+     [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("cgr_profile_enable", c_int32, [c_int32]),
     ("cgr_profile_collect", c_int32, []),
     ("cgr_profile_reset", None, []),

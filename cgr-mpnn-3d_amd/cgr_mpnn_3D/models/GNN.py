@@ -39,10 +39,11 @@ from .._amd import native
 from .._amd.functional import (LEVEL_FUSED, LEVEL_NODES, LEVEL_POOLED, gnn_encode,
                                gnn_encode_nodes, gnn_encode_nodes_predict, gnn_encode_predict,
                                gnn_forward, gnn_predict)
-from .._amd.pool import (aggregation_code, global_add_pool, global_max_pool, global_mean_pool,
-                         pooling_code)
+from .._amd.pool import (AttentionPool, aggregation_code, global_add_pool, global_max_pool,
+                         global_mean_pool, pooling_code)
 
-__all__ = ["GNN", "DMPNNConv", "global_add_pool", "global_mean_pool", "global_max_pool"]
+__all__ = ["GNN", "DMPNNConv", "global_add_pool", "global_mean_pool", "global_max_pool",
+           "AttentionPool"]
 
 
 def _as(t, dtype, dev):
@@ -219,11 +220,27 @@ class GNN(nn.Module):
             ff.in_features == self._modules["edge_to_node"].out_features
 
     # -- forward -------------------------------------------------------------------------------
-    def _cgr_run(self, data, level):
+    @staticmethod
+    def _cgr_graphs(data, dev):
+        """``(batch, graph_ptr, num_graphs)`` of a batch: ``ptr`` (on the GPU) gives the count
+        without a sync, else ``num_graphs``, else ``batch.max()`` (one sync)."""
+        batch = data.batch
+        if batch is None:
+            return None, None, 1
+        batch = _as(batch, torch.int64, dev)
+        ptr = getattr(data, "ptr", None)
+        if ptr is not None and ptr.numel() >= 2 and ptr.is_cuda:
+            graph_ptr = _as(ptr, torch.int64, ptr.device)
+            return batch, graph_ptr, graph_ptr.numel() - 1
+        ng = getattr(data, "num_graphs", None)
+        return batch, None, int(ng) if ng is not None else int(batch.max()) + 1
+
+    def _cgr_run(self, data, level, graphs=None):
         """Input handling and checks shared by ``forward`` (LEVEL_FUSED: the fused call, y [B]),
         ``encode`` (LEVEL_POOLED: the headless call, g [B, H]) and ``encode_nodes`` (LEVEL_NODES:
-        hn [N, H]), then the native call: its predict form when no gradient is wanted."""
-        x, edge_index, edge_attr, batch = data.x, data.edge_index, data.edge_attr, data.batch
+        hn [N, H]), then the native call: its predict form when no gradient is wanted.
+        ``graphs``: a ``_cgr_graphs`` result the caller already holds."""
+        x, edge_index, edge_attr = data.x, data.edge_index, data.edge_attr
         if not x.is_cuda:
             raise RuntimeError(
                 "cgr_mpnn_3D (MI355X) runs on the GPU only: move the model and the batch to "
@@ -257,18 +274,8 @@ class GNN(nn.Module):
         if edge_index.shape[1] % 2:
             raise RuntimeError("GNN: edge_index must hold reverse-edge pairs (GNN.py:136-138)")
 
-        graph_ptr = None
-        if batch is None:
-            num_graphs = 1
-        else:
-            batch = _as(batch, torch.int64, dev)
-            ptr = getattr(data, "ptr", None)
-            if ptr is not None and ptr.numel() >= 2 and ptr.is_cuda:
-                graph_ptr = _as(ptr, torch.int64, ptr.device)
-                num_graphs = graph_ptr.numel() - 1
-            else:
-                ng = getattr(data, "num_graphs", None)
-                num_graphs = int(ng) if ng is not None else int(batch.max()) + 1
+        batch, graph_ptr, num_graphs = graphs if graphs is not None else \
+            self._cgr_graphs(data, dev)
         if _config.strict and int(edge_index[1].max()) + 1 != x.shape[0]:
             # the reference's cat([x, s]) (GNN.py:106) fails when the last node has no in-edge
             raise RuntimeError(
@@ -326,16 +333,36 @@ class GNN(nn.Module):
         fingerprint: ``self.ffn(self.encode(data)).squeeze(-1)``.  Forward hooks registered on
         ``ffn`` do not change this routing (the fused call does not run the module, so they do
         not fire for the default head): read the fingerprint with ``encode``."""
+        if isinstance(self.pooling_fn, AttentionPool):
+            return self.ffn(self._cgr_attention(data)).squeeze(-1)
         if self._fused_head():
             return self._cgr_run(data, LEVEL_FUSED)
         return self.ffn(self._cgr_run(data, LEVEL_POOLED)).squeeze(-1)
+
+    def _cgr_attention(self, data):
+        """``pooling_fn(encode_nodes(data), batch, size=num_graphs, ptr=ptr)`` for an
+        ``AttentionPool`` readout: the native per-atom embedding, then the native gated-softmax
+        pool; the batch's graphs are resolved once for both (no second sync).  With a
+        gradient-bucket hook and gradients wanted the nodes level raises ``NotImplementedError``,
+        as ``encode`` does (the readout's and head's gradients are not in the hook's buffer)."""
+        if not data.x.is_cuda:
+            raise RuntimeError(
+                "cgr_mpnn_3D (MI355X) runs on the GPU only: move the model and the batch to "
+                "'cuda' (there is no CPU fallback)")
+        graphs = self._cgr_graphs(data, data.x.device)
+        hn = self._cgr_run(data, LEVEL_NODES, graphs)
+        batch, graph_ptr, num_graphs = graphs
+        return self.pooling_fn(hn, batch, size=num_graphs, ptr=graph_ptr)
 
     def encode(self, data):
         """The learned reaction fingerprint ``pooling_fn(h, batch)`` [B, H] (the input of ``ffn``,
         GNN.py:110), differentiable with respect to every encoder parameter, ``x`` and
         ``edge_attr``.  Same input handling, dropout keying and counter advance as ``forward``;
         under ``torch.no_grad()`` or when nothing requires grad, the forward-only form.  ``ffn``
-        takes no part, so it may be any module."""
+        takes no part, so it may be any module.  With ``pooling_fn=AttentionPool(H)`` it is that
+        module's pooled output."""
+        if isinstance(self.pooling_fn, AttentionPool):
+            return self._cgr_attention(data)
         return self._cgr_run(data, LEVEL_POOLED)
 
     def encode_nodes(self, data):

@@ -686,4 +686,58 @@ int cgr_segment_sum(const float* values, int64_t ld_values, const int32_t* index
   return 0;
 }
 
+// what the attention-pool pair shares: sizes, the segment source, the pointers both read
+static int attn_pool_check(const char* what, const float* x, int64_t ldx, int64_t N, int64_t H,
+                           const int64_t* batch, const int64_t* ptr, int64_t B,
+                           const float* weight) {
+  const std::string w(what);
+  CGR_CHECK(H > 0 && H < (1ll << 30), w + ": H must be >= 1");
+  CGR_CHECK(ldx >= H, w + ": ldx < H");
+  CGR_CHECK(N >= 0 && N < (1ll << 31) && B >= 0 && B < (1ll << 31), w + ": N or B out of range");
+  CGR_CHECK(B <= 1 || batch != nullptr || ptr != nullptr,
+            w + ": B > 1 needs batch or ptr (neither = one graph)");
+  CGR_CHECK(weight != nullptr && (N == 0 || x != nullptr), w + ": NULL pointer");
+  return 0;
+}
+
+int64_t cgr_attention_pool_workspace_bytes(int64_t B, int64_t H) {
+  if (B < 0 || H <= 0 || B >= (1ll << 31) || H >= (1ll << 30)) return -1;
+  return B * round_up(H, 4) * (int64_t)sizeof(float);
+}
+
+int cgr_attention_pool_forward(const float* x, int64_t ldx, int64_t N, int64_t H,
+                               const int64_t* batch, const int64_t* ptr, int64_t B,
+                               const float* weight, const float* bias, const uint8_t* mask,
+                               float* g, float* alpha, void* stream) {
+  clear_stale_hip_error();
+  const int rc = attn_pool_check("cgr_attention_pool_forward", x, ldx, N, H, batch, ptr, B, weight);
+  if (rc) return rc;
+  CGR_CHECK((B == 0 || g != nullptr) && (N == 0 || alpha != nullptr),
+            "cgr_attention_pool_forward: NULL pointer");
+  HIP_RET(attn_pool_fwd(x, ldx, N, (int)H, batch, ptr, B, weight, bias, mask, g, alpha,
+                        (hipStream_t)stream));
+  return 0;
+}
+
+int cgr_attention_pool_backward(const float* x, int64_t ldx, int64_t N, int64_t H,
+                                const int64_t* batch, const int64_t* ptr, int64_t B,
+                                const float* weight, const float* alpha, const float* dg,
+                                float* dx, float* dw, void* workspace, void* stream) {
+  clear_stale_hip_error();
+  const int rc =
+      attn_pool_check("cgr_attention_pool_backward", x, ldx, N, H, batch, ptr, B, weight);
+  if (rc) return rc;
+  CGR_CHECK((B == 0 || dg != nullptr) && (N == 0 || alpha != nullptr),
+            "cgr_attention_pool_backward: NULL pointer");
+  CGR_CHECK(dw == nullptr || B == 0 ||
+                (workspace != nullptr && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0),
+            "cgr_attention_pool_backward: dw needs a 16-byte aligned workspace "
+            "(cgr_attention_pool_workspace_bytes)");
+  if (B == 0 && dw)  // no graph: the sum over none
+    HIP_RET(hipMemsetAsync(dw, 0, (size_t)H * sizeof(float), (hipStream_t)stream));
+  HIP_RET(attn_pool_bwd(x, ldx, N, (int)H, batch, ptr, B, weight, alpha, dg, dx, dw,
+                        static_cast<float*>(workspace), (hipStream_t)stream));
+  return 0;
+}
+
 }  // extern "C"

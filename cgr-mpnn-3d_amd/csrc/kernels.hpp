@@ -181,4 +181,17 @@ struct ScalarReduceJobs {
 hipError_t reduce_partials(const float* part, int nb, const ScalarReduceJobs& jobs,
                            hipStream_t st);
 
+// attention pooling (attn_pool.hip): g [B, H], alpha [N] from x [N, ldx], the gate w [H], bias [1]
+// (nullable), mask [N] (nullable); graph b's atoms from ptr [B + 1], else from the sorted batch
+// [N], else all N.  One launch.
+hipError_t attn_pool_fwd(const float* x, int64_t ldx, int64_t N, int H, const int64_t* batch,
+                         const int64_t* ptr, int64_t B, const float* w, const float* bias,
+                         const uint8_t* mask, float* g, float* alpha, hipStream_t st);
+// its backward from dg [B, H]: dx [N, H] and dw [H] (either nullable); dwp [B, round_up(H, 4)] is
+// the per-graph dw partials (16-byte aligned; only read and written when dw is wanted).  One
+// launch, and the partials' reduction when dw is wanted.
+hipError_t attn_pool_bwd(const float* x, int64_t ldx, int64_t N, int H, const int64_t* batch,
+                         const int64_t* ptr, int64_t B, const float* w, const float* alpha,
+                         const float* dg, float* dx, float* dw, float* dwp, hipStream_t st);
+
 }  // namespace cgr

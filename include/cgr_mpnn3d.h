@@ -491,6 +491,42 @@ int cgr_huber_loss_backward(const float* input, const float* target, const float
                             int64_t n, int32_t reduction_mean, double delta, float* grad_input,
                             float* grad_target, void* stream);
 
+/* Attention pooling over atom embeddings (added within ABI 9; no reference counterpart: the
+ * readout GNN.encode_nodes was added for, as one kernel each way).  A gated softmax over each
+ * graph's atoms:
+ *   s_v = x[v].weight + bias[0] ; alpha_v = exp(s_v - max_u s_u) / sum_u exp(s_u - max_u s_u)
+ *   over the unmasked atoms u of v's graph (alpha_v = 0 for a masked atom) ; g[b] = sum_v alpha_v x[v]
+ * x: device [N, H] fp32, row stride ldx >= H (floats).  Graph b's atoms are rows [ptr[b],
+ * ptr[b + 1]) when ptr (device int64 [B + 1]) is given; else the rows whose id in batch (device
+ * int64 [N], sorted ascending) is b, found by binary search inside the kernel; with neither,
+ * B == 1 and the one graph is all N rows.  weight [H]; bias [1] or NULL; mask: device bytes [N],
+ * nonzero = the atom takes part, or NULL.  Outputs: g [B, H] (row stride H), alpha [N].  Every
+ * atom is expected to belong to one of the B graphs: alpha and dx rows of atoms outside all of
+ * them are not written.
+ * A graph without unmasked atoms gives a g row of +0.0 and alpha 0: nothing is divided by its zero
+ * sum.  The maximum is subtracted, so scores of any magnitude are safe.  One workgroup per graph,
+ * atoms summed in order: deterministic, and a graph's results depend on its own rows only.
+ * forward: one launch.
+ * backward, from dg [B, H] (row stride H) and the forward's alpha, with t_v = dg[b].x[v],
+ *   c_b = sum_v alpha_v t_v, ds_v = alpha_v (t_v - c_b):
+ *   dx[v] = alpha_v dg[b] + ds_v weight   [N, H], row stride H (masked atoms: exact zeros)
+ *   dw    = sum_v ds_v x[v]               [H]
+ * either may be NULL.  The bias has no gradient entry: the softmax is invariant to a shift of
+ * every score, so d/d bias is exactly 0.  workspace: cgr_attention_pool_workspace_bytes(B, H)
+ * bytes, 16-byte aligned, needed (and touched) only when dw is wanted: one dw partial per graph,
+ * summed over the graphs in a fixed order by a second launch.
+ * Refused before any launch: H <= 0, ldx < H, N or B out of range, B > 1 without batch and ptr,
+ * NULL required pointers, a misaligned workspace. */
+int64_t cgr_attention_pool_workspace_bytes(int64_t B, int64_t H);
+int cgr_attention_pool_forward(const float* x, int64_t ldx, int64_t N, int64_t H,
+                               const int64_t* batch, const int64_t* ptr, int64_t B,
+                               const float* weight, const float* bias, const uint8_t* mask,
+                               float* g, float* alpha, void* stream);
+int cgr_attention_pool_backward(const float* x, int64_t ldx, int64_t N, int64_t H,
+                                const int64_t* batch, const int64_t* ptr, int64_t B,
+                                const float* weight, const float* alpha, const float* dg,
+                                float* dx, float* dw, void* workspace, void* stream);
+
 /* Instrumentation (no reference counterpart): per-kernel-class device time measured with HIP
  * events recorded on the launch stream around every launch of cgr_gnn_forward/_backward.
  * Off by default; do not enable while capturing a graph.  cgr_profile_collect() waits for the

@@ -27,6 +27,11 @@ step; nothing else crosses the host/device boundary until ``epoch_loss()``.
 A batch that does not fit the capacities (or whose pad graph would exceed the pad-degree bound)
 runs the same step eagerly on ``store.collate(ids)`` and is counted in ``fallbacks``.  There is
 no non-native path: both forms run the HIP kernels.
+
+The zero-weight slots leave the loss as ``loss_fn(pred * mask, y * mask)``, which needs a ``[B +
+1]`` prediction and a loss term that is 0 at (0, 0).  A loss whose class sets ``pads_by_weight``
+(``GaussianNLLLoss`` on a ``MeanVarianceHead`` model, ``[B + 1, 2]``) is called as ``loss_fn(pred,
+y, weight=mask)`` instead: the native losses skip an element of weight 0.
 """
 
 from __future__ import annotations
@@ -73,7 +78,7 @@ class CapturedTrainer:
         self._batch = store.alloc_padded(B, self.node_cap, self.edge_cap)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)  # the last step's loss
         self.loss_total = torch.zeros((), dtype=torch.float32, device=dev)
-        self._pred = torch.zeros(B + 1, dtype=torch.float32, device=dev)
+        self._pred = None  # static [B + 1] (+ the model's trailing dims), shaped at first predict
         self._train_graph = None
         self._predict_graph = None
 
@@ -123,7 +128,11 @@ class CapturedTrainer:
         b = self._collate_static()
         self.optimizer.zero_grad(set_to_none=True)
         pred = self.model(b)
-        loss = self.loss_fn(pred * b.mask, b.y * b.mask)
+        if getattr(self.loss_fn, "pads_by_weight", False):
+            # (a [B + 1, 2] output, and a term that is not 0 at (0, 0): GaussianNLLLoss)
+            loss = self.loss_fn(pred, b.y, weight=b.mask)
+        else:
+            loss = self.loss_fn(pred * b.mask, b.y * b.mask)
         loss.backward()
         self.optimizer.step()
         self._account(loss)
@@ -138,7 +147,10 @@ class CapturedTrainer:
 
     def _padded_predict(self):
         b = self._collate_static()
-        self._pred.copy_(self.model(b))
+        out = self.model(b)
+        if self._pred is None:  # the first (eager warm-up) call: [B + 1], or [B + 1, 2] for a
+            self._pred = torch.zeros_like(out)  # mean-variance head
+        self._pred.copy_(out)
 
     # -- capture ---------------------------------------------------------------------------------
     def _snapshot(self):
@@ -201,7 +213,8 @@ class CapturedTrainer:
     @torch.no_grad()
     def predict(self, ids):
         """Eval-mode predictions for ``ids`` from a second captured graph (forward only): a view
-        of the first ``len(ids)`` entries of a static tensor, overwritten by the next call."""
+        of the first ``len(ids)`` rows of a static tensor (``[n]``, or ``[n, 2]`` for a
+        mean-variance head), overwritten by the next call."""
         ids, full, n = self._full_ids(ids)
         was_training = self.model.training
         if not self._fits(full):

@@ -32,3 +32,24 @@ def predict(model, store, ids=None, batch_size: int = 4096) -> torch.Tensor:
     if not outs:
         return torch.empty(0, device=store.device)
     return torch.cat(outs)
+
+
+@torch.no_grad()
+def predict_ensemble(models, store, ids=None, batch_size: int = 4096):
+    """``(mean, aleatoric, epistemic)`` per reaction from an ensemble: ``predict`` of every member,
+    then ``mean`` = the mean of the members' means, ``aleatoric`` = the mean of the members'
+    variances (``None`` when the members return ``[n]``, a point estimate each) and ``epistemic``
+    = the population variance of the members' means.  Members return ``[n, 2]`` (mean, variance:
+    ``MeanVarianceHead``) or ``[n]``, all alike."""
+    models = list(models)
+    if not models:
+        raise ValueError("predict_ensemble: no models")
+    outs = [predict(m, store, ids, batch_size) for m in models]
+    if any(o.shape != outs[0].shape for o in outs) or outs[0].dim() not in (1, 2) or \
+            (outs[0].dim() == 2 and outs[0].shape[1] != 2):
+        raise ValueError("predict_ensemble: every member must return [n] or [n, 2], all alike; "
+                         f"got {[tuple(o.shape) for o in outs]}")
+    out = torch.stack(outs)  # [M, n] or [M, n, 2]
+    mus = out if out.dim() == 2 else out[..., 0]
+    aleatoric = None if out.dim() == 2 else out[..., 1].mean(0)
+    return mus.mean(0), aleatoric, mus.var(0, unbiased=False)

@@ -182,6 +182,25 @@ SIGNATURES = [
     ("cgr_attention_pool_backward", c_int32,
      [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the mean-variance head (added within ABI 9): g, ldg, B, H, w_mu, [b_mu,] w_var, ...
+    ("cgr_meanvar_head_forward", c_int32,
+     [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+      c_void_p, c_void_p, c_void_p]),
+    ("cgr_meanvar_head_backward", c_int32,
+     [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p]),
+    # the weighted losses (added within ABI 9): mu, mu_stride, var, var_stride, target, weight, ...
+    ("cgr_gaussian_nll_loss_forward", c_int32,
+     [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+      c_double, c_void_p, c_void_p]),
+    ("cgr_gaussian_nll_loss_backward", c_int32,
+     [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+      c_double, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    ("cgr_weighted_loss_forward", c_int32,
+     [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_double, c_void_p, c_void_p]),
+    ("cgr_weighted_loss_backward", c_int32,
+     [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_double, c_void_p,
+      c_void_p, c_void_p]),
     ("cgr_profile_enable", c_int32, [c_int32]),
     ("cgr_profile_collect", c_int32, []),
     ("cgr_profile_reset", None, []),

@@ -39,11 +39,12 @@ from .._amd import native
 from .._amd.functional import (LEVEL_FUSED, LEVEL_NODES, LEVEL_POOLED, gnn_encode,
                                gnn_encode_nodes, gnn_encode_nodes_predict, gnn_encode_predict,
                                gnn_forward, gnn_predict)
+from .._amd.heads import MeanVarianceHead
 from .._amd.pool import (AttentionPool, aggregation_code, global_add_pool, global_max_pool,
                          global_mean_pool, pooling_code)
 
 __all__ = ["GNN", "DMPNNConv", "global_add_pool", "global_mean_pool", "global_max_pool",
-           "AttentionPool"]
+           "AttentionPool", "MeanVarianceHead"]
 
 
 def _as(t, dtype, dev):

@@ -527,6 +527,71 @@ int cgr_attention_pool_backward(const float* x, int64_t ldx, int64_t N, int64_t 
                                 const float* weight, const float* alpha, const float* dg,
                                 float* dx, float* dw, void* workspace, void* stream);
 
+/* Mean-variance head on the pooled fingerprint (added within ABI 9; no reference counterpart: the
+ * head of a heteroscedastic regression, one launch each way).  g: device [B, H] fp32, row stride
+ * ldg >= H (floats), the output of cgr_gnn_encode or of the attention pool.
+ *   mu[b] = g[b].w_mu + b_mu[0] ; raw[b] = g[b].w_var + b_var[0]
+ *   var[b] = softplus(raw[b]) + min_var     (torch's softplus: beta 1, raw itself above 20)
+ * w_mu, w_var [H]; b_mu, b_var [1] or NULL (= 0).  Outputs: out [B, 2] interleaved (out[b, 0] =
+ * mu, out[b, 1] = var) and raw [B], what the backward reads (NULL: not stored).
+ * backward, from dout [B, 2] and the forward's raw, with draw[b] = dout[b, 1] sigmoid(raw[b]) (1
+ * above the threshold):
+ *   dg[b] = dout[b, 0] w_mu + draw[b] w_var                       [B, H], row stride H
+ *   dW    = (sum_b dout[b, 0] g[b], sum_b draw[b] g[b])           [2, H]
+ *   db    = (sum_b dout[b, 0], sum_b draw[b])                     [2]
+ * each may be NULL and is then not computed.  Every sum has a fixed shape and order (no atomics):
+ * results are reproducible, and a row of out and of dg is the same bits whether its graph is
+ * computed alone or in any batch.  No workspace.
+ * Refused before any launch: H <= 0, ldg < H, B out of range, NULL required pointers (g, w_mu,
+ * w_var; out; raw and dout in the backward), a min_var that is negative or not finite. */
+int cgr_meanvar_head_forward(const float* g, int64_t ldg, int64_t B, int64_t H,
+                             const float* w_mu, const float* b_mu, const float* w_var,
+                             const float* b_var, double min_var, float* out, float* raw,
+                             void* stream);
+int cgr_meanvar_head_backward(const float* g, int64_t ldg, int64_t B, int64_t H,
+                              const float* w_mu, const float* w_var, const float* raw,
+                              const float* dout, float* dg, float* dW, float* db, void* stream);
+
+/* torch.nn.GaussianNLLLoss (added within ABI 9).  mu and var are read with an element stride
+ * (mu[i * mu_stride], var[i * var_stride]: 1 for contiguous tensors; 2 with var = mu + 1 for the
+ * two columns of the head's out [n, 2] in place); target, weight: device [n] fp32, weight may be
+ * NULL (= all 1).  With v = max(var, eps) and d = mu - target:
+ *   *loss = sum_i w_i (0.5 (log v_i + d_i^2 / v_i) + (full ? 0.5 log 2 pi : 0))   (/ n)
+ *   grad_mu = w (d / v) grad_loss[0] (/ n) ; grad_target = -grad_mu
+ *   grad_var = w 0.5 (1 / v - d^2 / v^2) grad_loss[0] (/ n), evaluated at the clamped v and
+ *     handed to var unchanged also where var < eps (torch's clamp is not differentiated)
+ * grad_mu and grad_var are written at [i * grad_stride] (grad_var = grad_mu + 1, stride 2: one
+ * [n, 2] tensor); each gradient may be NULL.  The mean divides by n whatever the weights are (as
+ * torch's weighted losses do).  An element with w_i == 0 is skipped, not multiplied: it adds
+ * nothing and its gradients are +0.0 whatever mu, var and target hold there (NaN, inf, var <= 0).
+ * A negative var is not an error here (torch raises, at the price of a host sync).
+ * One launch each, deterministic.  Refused before any launch: n < 0, a stride < 1, eps that is
+ * not > 0 and finite, NULL required pointers. */
+int cgr_gaussian_nll_loss_forward(const float* mu, int64_t mu_stride, const float* var,
+                                  int64_t var_stride, const float* target, const float* weight,
+                                  int64_t n, int32_t reduction_mean, int32_t full, double eps,
+                                  float* loss, void* stream);
+int cgr_gaussian_nll_loss_backward(const float* mu, int64_t mu_stride, const float* var,
+                                   int64_t var_stride, const float* target, const float* weight,
+                                   const float* grad_loss, int64_t n, int32_t reduction_mean,
+                                   double eps, float* grad_mu, float* grad_var,
+                                   int64_t grad_stride, float* grad_target, void* stream);
+
+/* The weighted forms of the MSE / L1 / Huber pairs above (added within ABI 9): sum_i w_i l_i
+ * (/ n), grad_input = w_i l_i' grad_loss[0] (/ n), grad_target = -grad_input, with the same terms
+ * l_i.  weight: device [n] fp32, required (the unweighted losses are the entries above); delta is
+ * read for CGR_LOSS_HUBER only.  An element with w_i == 0 is skipped, as in the Gaussian loss: it
+ * adds nothing and its gradients are +0.0 whatever input and target hold there.  One launch each,
+ * deterministic. */
+enum cgr_weighted_loss { CGR_LOSS_MSE = 0, CGR_LOSS_L1 = 1, CGR_LOSS_HUBER = 2 };
+int cgr_weighted_loss_forward(int32_t kind, const float* input, const float* target,
+                              const float* weight, int64_t n, int32_t reduction_mean,
+                              double delta, float* loss, void* stream);
+int cgr_weighted_loss_backward(int32_t kind, const float* input, const float* target,
+                               const float* weight, const float* grad_loss, int64_t n,
+                               int32_t reduction_mean, double delta, float* grad_input,
+                               float* grad_target, void* stream);
+
 /* Instrumentation (no reference counterpart): per-kernel-class device time measured with HIP
  * events recorded on the launch stream around every launch of cgr_gnn_forward/_backward.
  * Off by default; do not enable while capturing a graph.  cgr_profile_collect() waits for the

@@ -22,8 +22,13 @@ its own ``max_grad_norm`` (a group with ``None`` is not scaled; ``float("inf")``
 clips).  One more native launch per param group (``cgr_grad_sumsq``), no host read, capturable; a
 captured step replays the float it was captured with.  Two deviations from torch: ``p.grad`` is
 left unscaled (the scaling happens inside the Adam kernel), and a non-finite norm skips the whole
-step -- parameters, moments and ``state["step"]`` stay, ``skipped_steps`` counts it -- where torch
-would write NaN into every parameter.  ``grad_norm`` is the last step's norm before clipping.
+step -- parameters, moments and ``state["step"]`` stay, ``skipped_steps`` counts it.  The norm is
+not finite in two cases, and torch differs in each.  With a NaN among the gradients torch's norm
+and coefficient are NaN and it writes NaN into every parameter.  With an infinite norm -- an
+``inf`` among the gradients, or finite gradients whose squares overflow in fp32 (``|g|`` above
+~1.8e19) -- torch's coefficient is 0 and it steps with zeroed gradients (weight decay and the
+decaying moments still move the parameters; an ``inf`` element itself becomes ``inf * 0`` = NaN).
+``grad_norm`` is the last step's norm before clipping.
 """
 
 from __future__ import annotations
